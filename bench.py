@@ -1,7 +1,12 @@
 """Headline benchmark of the hot path (BASELINE.json: images/sec at 1024^2, ViT-B; kernel rooflines).
 
-    python bench.py --gpus N --steps K --warmup W [--config vitb|vitl|swinb]
+    python bench.py --gpus N --steps K --warmup W [--config vitb|vitl|swinb] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, K timed steps, the outputs of the
+last timed step to DIR when --dump-outputs is given, one JSON line.  Every other leg described below (the extra event-timed
+steps, the other RNG mode / precision / configurations, the roll-out check against the dense product, the training step,
+the CPU baseline) runs only with --full.
 
 One STEP = one pass of the hot path over one batch.  `--config vitb` (default, the configuration the metric is quoted
 on = BASELINE configs[1] per GPU, configs[2] at 8 GPUs): MAE-ViT-Base, 1024x1024, 2 images, 3 point-labelled objects per
@@ -20,11 +25,18 @@ Images shard over GPUs with no data-path collective in this (forward / no-grad) 
 
 Rank 0 prints ONE JSON line.  `roofline` = the dominant kernel (flash SDPA forward, MFMA-bound) timed with
 HIP events on its launch stream inside the timed region; `roofline_affinity` = the mean-shift token-affinity
-call (HBM-bound, algorithmic bytes of SURVEY 8d); `cpu_baseline` = the CPU oracle port timed on this box's
+call (HBM-bound, algorithmic bytes of SURVEY 8d).  With --full: `cpu_baseline` = the CPU oracle port timed on this box's
 host cores on a bounded sample (rank 0, N=1 only); `train` = the DDP training step (forward + attention shift + the
 RoI head's real losses on seeded proposals + backward + bucketed RCCL gradient all-reduce + AdamW): always at N > 1,
 where it is what exercises xGMI, and at N = 1 unless --train-steps 0.  A watchdog prints the headline record without the
 training leg if that leg does not finish (so an RCCL problem can never take the scaling number down).
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the LAST timed step handed to its caller as DIR/<name>.npy
+(float32; float64 for float64 and 32- / 64-bit integer values): `labels.*` = the dict seed_pseudo_gt returned (boxes, mask points, part centres,
+instance maps, pseudo masks, ...), `backbone.*` = the backbone's outputs of the same step (last_feat, FPN maps, point
+head).  Arrays above a size cap are a fixed seeded sample of their elements (64 MB in all at most).  Inputs, weights
+and the RNG seed are functions of the arguments alone, so two builds run with the same arguments can be compared
+array for array.
 """
 import argparse
 import json
@@ -107,7 +119,10 @@ def synthetic_proposals(shift, device, n=1000):
     return out
 
 
-def build(device, rng_mode="fast", train=False, ranks=None, mil=False, compute_dtype=torch.bfloat16):
+def build(device, rng_mode="fast", train=False, ranks=None, mil=False, compute_dtype=torch.bfloat16, check_rollout=True):
+    """-> step().  check_rollout=False leaves out the one-time comparison of the first call's roll-out rows with the dense
+    product (a plain benchmark run).  The forward steps carry `step.keep`: set it to a dict and every call leaves the
+    backbone's outputs and its own return value there (--dump-outputs)."""
     import attentionshift_amd as A
     from attentionshift_amd import synthetic
 
@@ -121,9 +136,13 @@ def build(device, rng_mode="fast", train=False, ranks=None, mil=False, compute_d
         img = synthetic.images(CFG["batch"], CFG["img"], CFG["img"], seed=rank).to(device)
 
         def swin_step():
-            return bb(img)
+            res = bb(img)
+            if swin_step.keep is not None:
+                swin_step.keep.update(backbone=res, labels=None)
+            return res
 
         swin_step.head = None
+        swin_step.keep = None
         return swin_step
 
     bb = A.build_backbone(dict(type="VisionTransformerDet", img_size=CFG["img"], patch_size=CFG["patch"],
@@ -150,7 +169,8 @@ def build(device, rng_mode="fast", train=False, ranks=None, mil=False, compute_d
     gt_labels = [(s["labels"] % CFG["num_classes"]).to(device) for s in shift]
 
     class BenchHead(A.AttnShiftRoIHead):
-        rollout_check = None          # set by the FIRST call (a warm-up step): the real rows vs the dense route
+        # set by the FIRST call (a warm-up step): the real rows vs the dense route; False = the check is not wanted
+        rollout_check = None if check_rollout else False
 
         def rollout_cams(self, attns, num_proposals, pos_inds=None):
             rows = super().rollout_cams(attns, num_proposals, pos_inds)         # real roll-out of this pass
@@ -197,9 +217,12 @@ def build(device, rng_mode="fast", train=False, ranks=None, mil=False, compute_d
                 out["feature"].result()                # the step ends with the FPN maps valid on the caller's stream
             if "point_head_ready" in out:              # ... and the point head's outputs (queued on its own stream)
                 torch.cuda.current_stream().wait_event(out["point_head_ready"])
+            if step.keep is not None:
+                step.keep.update(backbone=out, labels=res)
             return res
 
         step.head = head
+        step.keep = None
         return step
 
     # DDP training step (BASELINE configs[2] shape per GPU; mmdet/apis/train.py:95-100 + two_stage_point_align.py:75-157
@@ -408,6 +431,58 @@ def cpu_baseline(only_threads=None):
                         f"({t_shift:.2f}s); timed with {' and '.join(rates)} torch threads on {host_cores} host cores, faster one reported"))
 
 
+DUMP_BYTES = 60 * 10 ** 6              # --dump-outputs: the arrays of one dump (64 MB with room for the file headers)
+DUMP_ARRAY_ELEMS = 1 << 19            # ... and one array above this many elements is written as a sample of that size
+BACKBONE_OUTPUTS = ("last_feat", "feature", "org_feats", "point_tokens", "outputs_class", "outputs_coord")
+
+
+def output_leaves(obj, prefix):
+    """Flatten what a step returned (dicts / lists / tuples of tensors, numpy arrays and numbers) into [(name, array-like)]
+    with dotted names; a list of plain numbers is one array.  Anything else (None, strings, opaque state) is left out."""
+    import numpy as np
+    if isinstance(obj, (torch.Tensor, np.ndarray)):
+        return [(prefix, obj)]
+    if isinstance(obj, (bool, int, float, np.number)):
+        return [(prefix, np.asarray(obj))]
+    if isinstance(obj, dict):
+        return [leaf for k in sorted(obj, key=str) for leaf in output_leaves(obj[k], f"{prefix}.{k}")]
+    if isinstance(obj, (list, tuple)):
+        if obj and all(isinstance(v, (bool, int, float, np.number)) for v in obj):
+            return [(prefix, np.asarray(obj))]
+        return [leaf for i, v in enumerate(obj) for leaf in output_leaves(v, f"{prefix}.{i}")]
+    return []
+
+
+def dump_outputs(keep, path):
+    """Write the outputs of one step (step.keep) as path/<name>.npy; see the module docstring.  -> {name: shape}."""
+    import numpy as np
+    bb_out = keep.get("backbone")
+    if isinstance(bb_out, dict):
+        bb_out = {k: (v.result() if hasattr(v, "result") else v) for k, v in bb_out.items() if k in BACKBONE_OUTPUTS}
+    leaves = output_leaves(keep.get("labels"), "labels") + output_leaves(bb_out, "backbone")
+    sizes = [int(np.prod(v.shape)) for _, v in leaves]
+    cap = DUMP_ARRAY_ELEMS
+    while sum(min(n, cap) for n in sizes) * 8 > DUMP_BYTES:       # (many large arrays: smaller samples of each)
+        cap = cap * 3 // 4
+    os.makedirs(path, exist_ok=True)
+    if torch.cuda.is_initialized():
+        torch.cuda.synchronize()
+    written, total = {}, 0
+    for name, v in leaves:
+        t = v.detach() if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
+        shape = list(t.shape)
+        if t.numel() > cap:              # a fixed sample: the same (sorted, seeded) flat indices for every array of this size
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        wide = t.dtype in (torch.float64, torch.int64, torch.int32)          # (integers stay exact in float64)
+        arr = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+        written[name] = shape
+        total += arr.nbytes
+    assert total <= DUMP_BYTES, total
+    return written
+
+
 def timed(step, ranks, steps, per_rank=None):
     """K steps between barrier + synchronize on both sides; MAX over ranks.  per_rank (a dict) additionally receives each
     rank's own time up to its synchronize (before the closing barrier): the spread that the max hides."""
@@ -459,6 +534,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="vitb")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: extra event-timed steps, the other RNG mode, the fp32 path, the "
+                         "MIL selector, the other configurations, the roll-out check, the training step, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0, help=argparse.SUPPRESS)     # child mode of cpu_baseline()
     ap.add_argument("--train-steps", type=int, default=5, help="steps of the DDP training-step leg (0 = skip)")
@@ -469,6 +549,8 @@ def main():
     if a.cpu_sample > 0:
         cpu_baseline(only_threads=a.cpu_sample)
         return
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     what, arg = launch_plan(a.gpus, os.environ, sys.argv[1:], torch.cuda.device_count())
     if what == "error":
         print(f"bench.py: {arg}", file=sys.stderr, flush=True)
@@ -507,7 +589,9 @@ def main():
     # AS_RNG_MODE (default fast); the reference-stream rate is measured right after and reported next to it.
     rng_mode = os.environ.get("AS_RNG_MODE", "fast")
     vit = CFG["backbone"] == "vit"
-    step = build(device, rng_mode)
+    step = build(device, rng_mode, check_rollout=a.full)
+    if a.dump_outputs and rank == 0:
+        step.keep = {}
     with torch.no_grad():
         for _ in range(a.warmup):
             step()
@@ -518,8 +602,12 @@ def main():
         elapsed = timed(step, ranks, a.steps)
     timing = ops.collect_timing()
     ops.disable_timing()
+    dumped = None
+    if step.keep is not None:
+        dumped = dump_outputs(step.keep, a.dump_outputs)
+        step.keep = None
     block_timing = {}
-    if vit and os.environ.get("AS_BENCH_EVENTS", "1") == "1":
+    if a.full and vit and os.environ.get("AS_BENCH_EVENTS", "1") == "1":
         # the attention BLOCK (A1 + A2 = QKV projection + SDPA + output projection) against the MFMA peak.  Its
         # three launches are timed in a few extra steps AFTER the headline's timed region (six event records per layer would
         # otherwise sit inside it)
@@ -555,7 +643,10 @@ def main():
                      "index outputs are bit-exact in both",
         "config": {"workload": CFG["workload"], "name": a.config, "global_batch": world * B,
                    "parallelism": f"dp{world} (image sharding, no data-path collective)"},
+        "full": a.full,
     }
+    if dumped is not None:
+        rec["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": len(dumped)}
     if not vit and "window_attn_fwd" in timing:
         # Swin (config 5): the fused window attention is HBM-bound -- its algorithmic traffic is one read of the qkv grid
         # and one write of the output (49 x 49 x 32 per window-head of MFMA work is ~1 % of the matrix peak)
@@ -571,9 +662,10 @@ def main():
     if vit:
         rec["rng_mode"] = rng_mode
         # the real roll-out rows of the first warm-up pass against the dense head-mean product (BenchHead.rollout_cams)
-        rec["rollout_check"] = getattr(step.head, "rollout_check", None)
+        if a.full:
+            rec["rollout_check"] = getattr(step.head, "rollout_check", None)
         other = "reference" if rng_mode == "fast" else "fast"
-        if os.environ.get("AS_BENCH_OTHER_RNG", "1") == "1":      # (0: profiling runs that want the headline leg alone)
+        if a.full and os.environ.get("AS_BENCH_OTHER_RNG", "1") == "1":      # (0: profiling runs that want the headline leg alone)
             step.head.rng_mode = other
             with torch.no_grad():
                 step()
@@ -667,7 +759,7 @@ def main():
             pass
         # the same step on the path that meets north_star's 1e-3 (compute_dtype=float32: exact-fp32 MFMA kernels,
         # tests/test_gpu_backbone_fullsize.py); the headline is the bf16 path BASELINE config 2 names
-        if os.environ.get("AS_BENCH_FP32", "1") == "1":
+        if a.full and os.environ.get("AS_BENCH_FP32", "1") == "1":
             try:
                 fstep = build(device, rng_mode, compute_dtype=torch.float32)
                 with torch.no_grad():
@@ -679,7 +771,7 @@ def main():
                 rec["images_per_sec_fp32_parity_path"] = None
                 rec["fp32_parity_path_error"] = f"{type(e).__name__}: {e}"[:200]
         # the same step with the trainable MIL head choosing the roll-out depth from RoI-aligned features (stdroi:2308-2312)
-        if os.environ.get("AS_BENCH_MIL", "1") == "1":
+        if a.full and os.environ.get("AS_BENCH_MIL", "1") == "1":
             del step
             torch.cuda.empty_cache()
             mstep = build(device, rng_mode, mil=True)
@@ -692,9 +784,9 @@ def main():
             del step
         torch.cuda.empty_cache()
 
-    # ---- short forward legs of the other BASELINE configurations (configs[3] ViT-L, configs[4] Swin-B), so that the
-    # driver's default invocation times them too; the headline numbers above are not affected ----
-    if a.config == "vitb" and a.other_configs:
+    # ---- short forward legs of the other BASELINE configurations (configs[3] ViT-L, configs[4] Swin-B), so that one
+    # --full invocation times them too; the headline numbers above are not affected ----
+    if a.full and a.config == "vitb" and a.other_configs:
         rec["other_configs"] = {}
         for name in [n for n in a.other_configs.split(",") if n in CONFIGS and n != "vitb"]:
             try:
@@ -747,8 +839,8 @@ def main():
         if rank == 0:
             os.write(real_stdout, (json.dumps(rec) + "\n").encode())
 
-    # ---- the DDP training step: default at N > 1 (that is where RCCL over xGMI runs), optional at N = 1 ----
-    if vit and a.train_steps > 0:
+    # ---- the DDP training step (--full): default at N > 1 (that is where RCCL over xGMI runs), optional at N = 1 ----
+    if a.full and vit and a.train_steps > 0:
         def give_up():
             rec["train"] = {"error": f"training leg did not finish within {a.train_timeout:.0f}s (watchdog)"}
             emit()
@@ -827,7 +919,7 @@ def main():
         except Exception:                                   # noqa: BLE001
             pass
 
-    if rank == 0 and world == 1 and a.config == "vitb" and not a.no_cpu_baseline and not emitted.is_set():
+    if a.full and rank == 0 and world == 1 and a.config == "vitb" and not a.no_cpu_baseline and not emitted.is_set():
         rec["cpu_baseline"] = cpu_baseline()
     emit()
     ranks.close()

@@ -24,12 +24,12 @@ ro, blk, aff, tr = rec["roofline"], rec.get("roofline_attention_block", {}), rec
 oc = rec.get("other_configs", {})
 cpu = rec.get("cpu_baseline", {})
 rows = [
-    ("hot path, BASELINE config 2 (ViT-B, 1024², 2 images/GPU, 3 objects), `python bench.py`",
+    ("hot path, BASELINE config 2 (ViT-B, 1024², 2 images/GPU, 3 objects), `python bench.py --full`",
      f"**{rec['value']:.1f} images/s** ({rec['ms_per_step']:.3f} ms/step); " + ab_text +
      f"{rec.get('images_per_sec_fp32_parity_path', float('nan'))} with `compute_dtype=float32` (the 1e-3 parity path); "
      f"{rec.get('images_per_sec_reference_rng', float('nan')):.1f} with the reference's literal RNG stream, "
      f"{rec.get('images_per_sec_mil_selector', float('nan')):.1f} with the MIL head choosing the roll-out depth"),
-    ("config 4 (ViT-L, 1280², 1 image, 7 objects) / config 5 (Swin-B backbone, 1024², 2 images): legs of the default run",
+    ("config 4 (ViT-L, 1280², 1 image, 7 objects) / config 5 (Swin-B backbone, 1024², 2 images): legs of the `--full` run",
      f"{oc.get('vitl', {}).get('images_per_sec', float('nan')):.1f} images/s (SDPA at {oc.get('vitl', {}).get('sdpa_fwd', {}).get('frac', float('nan')):.3f} of peak) / "
      f"{oc.get('swinb', {}).get('images_per_sec', float('nan')):.1f} images/s"),
     ("flash attention forward (`as_sdpa_fwd`), HIP events inside the timed region",

@@ -6,8 +6,10 @@
 R=${1:-rXX}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+OUT=$_                                  # (bash: the last argument of the previous command = the directory just made)
 t0=$(date +%s)
-timeout 600 python bench.py > gpurun_out/${R}_bench_final.json 2> gpurun_out/${R}_bench_final.log
+# every leg of the benchmark (--full): the headline, the other RNG mode / precision / configurations, training step, CPU baseline
+timeout 600 python bench.py --full > $OUT/${R}_bench_final.json 2> $OUT/${R}_bench_final.log
 echo "default bench.py wall: $(( $(date +%s) - t0 )) s" | tee gpurun_out/${R}_bench_wall.txt
 AS_BENCH_EVENTS=0 AS_BENCH_OTHER_RNG=0 AS_BENCH_MIL=0 AS_BENCH_FP32=0 PROF_LINES=8 tools/prof_cmd.sh ${R}_bench_kernel_stats_final python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --train-steps 0 --other-configs "" > /dev/null 2>&1
 timeout 300 python tools/kernel_bench.py --reps 20 > gpurun_out/${R}_kernel_bench.jsonl 2>&1
