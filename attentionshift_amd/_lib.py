@@ -99,6 +99,9 @@ SIGNATURES = {
     "as_rank_draw_xy": (_c_int, [_c_void_p, _c_int] + [_c_void_p] * 4 + [_c_int, _c_int, ctypes.c_int64, _c_int, _c_void_p, _c_size_t]
                         + [_c_int] * 5 + [_c_void_p]),
     "as_instance_maps": (_c_int, [_c_void_p] * 2 + [_c_int] * 6 + [_c_void_p] * 3 + [_c_size_t, _c_void_p]),
+    "as_nms_workspace_bytes": (_c_size_t, [_c_int]),
+    "as_nms": (_c_int, [_c_void_p, _c_int, _c_float, _c_int] + [_c_void_p] * 3 + [_c_size_t, _c_void_p]),
+    "as_paste_masks": (_c_int, [_c_void_p] * 4 + [_c_int] * 8 + [_c_float, _c_void_p]),
 }
 
 _lib = None

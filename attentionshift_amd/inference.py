@@ -1,5 +1,6 @@
-"""Test-time post-processing of the RoI head (host-side tensor logic; restated from their definitions because mmcv's
-ops are absent here):
+"""Test-time post-processing of the RoI head (restated from their definitions because mmcv's ops are absent here).
+CPU tensors take the tensor-op route below; device tensors run NMS and the mask paste on the HIP kernels of
+csrc/detect_post.hip (ops.nms / ops.paste_masks), unless AS_POST_HOST=1 forces the tensor-op route there too (A/B):
 
     nms / multiclass_nms   mmcv.ops.nms (greedy, IoU without the +1 offset) + mmdet/core/post_processing/bbox_nms.py:
                            scores above score_thr, class-aware suppression through per-class coordinate offsets, the
@@ -9,19 +10,30 @@ ops are absent here):
     get_seg_masks          mae_mask_head_pointSup.py:277-375: sigmoid, paste, threshold, per-class lists
     bbox2result            mmdet/core/bbox/transforms.py: per-class [n,5] arrays
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import ops
 from .assign import bbox_overlaps
 from .bbox_loss import delta2bbox
 
 
-def nms(boxes, scores, iou_threshold):
-    """Greedy NMS; returns kept indices sorted by decreasing score."""
+def _on_device(t):
+    """True when `t` takes the HIP route: a device tensor, and the host route not forced."""
+    return t.is_cuda and os.environ.get("AS_POST_HOST") != "1"
+
+
+def nms(boxes, scores, iou_threshold, max_keep=-1):
+    """Greedy NMS; returns kept indices sorted by decreasing score (device route: at most max_keep of them when
+    max_keep > 0 -- the prefix of the full result; it takes up to 65535 boxes and raises beyond)."""
     if boxes.numel() == 0:
         return torch.zeros(0, dtype=torch.long, device=boxes.device)
     order = scores.argsort(descending=True, stable=True)
+    if _on_device(boxes):
+        return order[ops.nms(boxes[order].contiguous().float(), iou_threshold, max_keep)]
     iou = bbox_overlaps(boxes[order], boxes[order], eps=1e-12).cpu()
     n = iou.shape[0]
     alive = torch.ones(n, dtype=torch.bool)
@@ -49,7 +61,7 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, iou_threshold, max_num
     if bboxes.numel() == 0:
         return multi_bboxes.new_zeros(0, 5), labels
     offsets = labels.to(bboxes) * (bboxes.max() + 1)                        # boxes of different classes never overlap
-    keep = nms(bboxes + offsets[:, None], scores, iou_threshold)
+    keep = nms(bboxes + offsets[:, None], scores, iou_threshold, max_num)
     if max_num > 0:
         keep = keep[:max_num]
     return torch.cat((bboxes[keep], scores[keep, None]), dim=1), labels[keep]
@@ -77,6 +89,8 @@ def paste_masks(masks, boxes, img_h, img_w):
     n = masks.shape[0]
     if n == 0:
         return masks.new_zeros(0, img_h, img_w)
+    if _on_device(masks):
+        return ops.paste_masks(masks.float().contiguous(), None, boxes.float().contiguous(), img_h, img_w, False, 0)
     x0, y0, x1, y1 = torch.split(boxes, 1, dim=1)
     img_y = torch.arange(0, img_h, device=masks.device, dtype=torch.float32) + 0.5
     img_x = torch.arange(0, img_w, device=masks.device, dtype=torch.float32) + 0.5
@@ -93,6 +107,9 @@ def get_seg_masks(mask_pred, det_bboxes, det_labels, num_classes, ori_shape, sca
     cls_segms = [[] for _ in range(num_classes)]
     if mask_pred.shape[0] == 0:
         return cls_segms
+    if _on_device(mask_pred):
+        return _get_seg_masks_device(mask_pred, det_bboxes, det_labels, cls_segms, ori_shape, scale_factor, rescale,
+                                     mask_thr_binary, class_agnostic)
     probs = mask_pred.sigmoid()
     boxes = det_bboxes[:, :4]
     if rescale:
@@ -106,6 +123,26 @@ def get_seg_masks(mask_pred, det_bboxes, det_labels, num_classes, ori_shape, sca
     sel = probs[idx, torch.zeros_like(det_labels) if class_agnostic else det_labels][:, None]
     full = paste_masks(sel, boxes, img_h, img_w)
     full = (full >= mask_thr_binary) if mask_thr_binary >= 0 else (full * 255).to(torch.uint8)
+    full = full.cpu().numpy()
+    for i, lab in enumerate(det_labels.tolist()):
+        cls_segms[lab].append(full[i])
+    return cls_segms
+
+
+def _get_seg_masks_device(mask_pred, det_bboxes, det_labels, cls_segms, ori_shape, scale_factor, rescale, mask_thr_binary,
+                          class_agnostic):
+    """get_seg_masks on the device: sigmoid of the one class channel, paste and threshold in one kernel; the [n,H,W]
+    byte result is the only thing copied to the host."""
+    boxes = det_bboxes[:, :4]
+    if rescale:
+        img_h, img_w = ori_shape[:2]
+        boxes = boxes / boxes.new_tensor(scale_factor)
+    else:
+        sf = np.asarray(scale_factor, dtype=np.float64).reshape(-1)
+        w_scale, h_scale = (sf[0], sf[1]) if sf.size > 1 else (sf[0], sf[0])
+        img_h, img_w = int(np.round(ori_shape[0] * h_scale)), int(np.round(ori_shape[1] * w_scale))
+    full = ops.paste_masks(mask_pred.float().contiguous(), None if class_agnostic else det_labels.long().contiguous(),
+                           boxes.float().contiguous(), img_h, img_w, True, 1 if mask_thr_binary >= 0 else 2, mask_thr_binary)
     full = full.cpu().numpy()
     for i, lab in enumerate(det_labels.tolist()):
         cls_segms[lab].append(full[i])

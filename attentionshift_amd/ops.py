@@ -1099,3 +1099,47 @@ def roi_align_bwd(dout, rois, shape, out_size, spatial_scale, sampling_ratio=0, 
     _lib.check(lib.as_roi_align_bwd(_p(dout), _p(rois), _p(dfeat), B, H, W, C, rois.shape[0], int(out_size),
                                     float(spatial_scale), int(sampling_ratio), int(bool(aligned)), _stream()), "as_roi_align_bwd")
     return dfeat
+
+
+# ------------------------------------------------------------------------------------------------
+# Part C: test-time post-processing (csrc/detect_post.hip)
+# ------------------------------------------------------------------------------------------------
+def nms(boxes_sorted, iou_threshold, max_keep=-1):
+    """boxes_sorted [n,4] fp32 in decreasing-score order -> LongTensor of the kept positions (ascending) of greedy NMS
+    with IoU > iou_threshold (as_nms); max_keep > 0 stops after that many.  n <= 65535.  The result's length is data
+    dependent: one 4-byte count is read back."""
+    lib = _lib.load()
+    _chk(boxes_sorted, dtype=torch.float32)
+    if boxes_sorted.dim() != 2 or boxes_sorted.shape[1] != 4:
+        raise AttnShiftError(f"nms: boxes must be [n, 4], got {tuple(boxes_sorted.shape)}")
+    n = boxes_sorted.shape[0]
+    keep = torch.empty(n, device=boxes_sorted.device, dtype=torch.int64)
+    if n == 0:
+        return keep
+    count = torch.empty(1, device=boxes_sorted.device, dtype=torch.int32)
+    nbytes = lib.as_nms_workspace_bytes(n)
+    ws = torch.empty(nbytes, device=boxes_sorted.device, dtype=torch.uint8)
+    _lib.check(lib.as_nms(_p(boxes_sorted), n, float(iou_threshold), int(max_keep), _p(keep), _p(count), _p(ws), nbytes,
+                          _stream()), "as_nms")
+    return keep[:int(count.item())]
+
+
+def paste_masks(src, labels, boxes, H, W, apply_sigmoid, out_mode, thr=0.5):
+    """src [n,K,h,w] fp32, labels [n] int64 or None (channel 0), boxes [n,4] fp32 -> [n,H,W]: every detection's channel
+    resampled bilinearly onto the image grid of its box, zero outside it (as_paste_masks; the sampling rule of
+    inference.paste_masks).  apply_sigmoid takes the sigmoid of the source first.  out_mode 0: fp32 values; 1: bool
+    v >= thr; 2: uint8 levels (uint8)(v * 255).  A box of non-positive width or height gives v = 0 everywhere (the tensor-op
+    route yields NaN samples there: the same all-False mask in mode 1, NaN / undefined values in modes 0 / 2)."""
+    lib = _lib.load()
+    _chk(src, boxes, dtype=torch.float32)
+    _chk(labels, dtype=torch.int64)
+    if src.dim() != 4 or tuple(boxes.shape) != (src.shape[0], 4) or (labels is not None and labels.numel() != src.shape[0]):
+        raise AttnShiftError("paste_masks: src [n,K,h,w], boxes [n,4], labels [n]")
+    if out_mode not in (0, 1, 2):
+        raise AttnShiftError(f"paste_masks: out_mode {out_mode}")
+    n, K, h, w = src.shape
+    out = torch.empty(n, int(H), int(W), device=src.device, dtype=(torch.float32, torch.bool, torch.uint8)[out_mode])
+    if out.numel():
+        _lib.check(lib.as_paste_masks(_p(src), _p(labels), _p(boxes), _p(out), n, K, h, w, int(H), int(W),
+                                      int(bool(apply_sigmoid)), int(out_mode), float(thr), _stream()), "as_paste_masks")
+    return out

@@ -499,6 +499,35 @@ int as_chamfer_2d_fwd(const float* xyz1, const float* xyz2, float* dist1, float*
 int as_chamfer_2d_bwd(const float* xyz1, const float* xyz2, const float* gdist1, const float* gdist2, const int32_t* idx1,
                       const int32_t* idx2, float* gxyz1, float* gxyz2, int B, int n, int m, as_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Part C -- test-time post-processing of the RoI head (csrc/detect_post.hip)
+ * ------------------------------------------------------------------------------------------- */
+
+/* Greedy NMS, the mmcv.ops.nms behind mmdet/core/post_processing/bbox_nms.py:84 (batched_nms; IoU without the +1 offset):
+ * boxes_sorted [n,4] fp32 (x1,y1,x2,y2) ALREADY in decreasing-score order -> keep_idx [n] int64, the kept positions of
+ * that order, compacted and ascending; count [1] int32, how many.  Box j is dropped iff a kept box i < j has
+ * IoU(i, j) > iou_thr, with IoU = inter / max(area_i + area_j - inter, 1e-12) evaluated in fp32 exactly as the ATen ops of
+ * the host route round it (no contraction, correctly rounded divide, NaN propagating).  max_keep > 0 stops after that many
+ * kept boxes (the result is the prefix of the full one); <= 0 keeps all.  Workspace: the pair bit mask,
+ * as_nms_workspace_bytes(n) = n * ceil(n / 64) * 8 bytes (0 for n <= 0), 8-byte aligned; boxes 16-byte aligned.
+ * n == 0 writes count = 0 (only `count` is touched).  n > 65535 is AS_E_UNSUPPORTED: the mask would pass 512 MB. */
+size_t as_nms_workspace_bytes(int n);
+int as_nms(const float* boxes_sorted, int n, float iou_thr, int max_keep, long long* keep_idx, int* count, void* workspace,
+           size_t workspace_bytes, as_stream_t stream);
+
+/* The mask paste of mae_mask_head_pointSup.py:277-375 (get_seg_masks) and :411-480 (_do_paste_mask) in one pass:
+ *   src [n,K,h,w] fp32, labels [n] int64 = the channel of each detection (NULL: channel 0, the class-agnostic head),
+ *   boxes [n,4] fp32 (x0,y0,x1,y1) in output-image pixels, out [n,H,W].
+ * Output pixel (x, y) of detection i samples its channel bilinearly (grid_sample, align_corners = False, zero padding) at
+ *   gx = (x + 0.5 - x0) / (x1 - x0) * 2 - 1,  ix = ((gx + 1) * w - 1) / 2      (the same in y)
+ * after the sigmoid when apply_sigmoid (applied to the source values, as the reference takes the sigmoid first).
+ * out_mode 0: fp32 values; 1: bytes v >= thr ? 1 : 0; 2: bytes (uint8)(v * 255).  A sample outside (-1, w) x (-1, h)
+ * gives v = 0; so does a box of non-positive (or NaN) width or height -- where the reference's inf - inf samples are NaN,
+ * i.e. all-zero masks in mode 1 and undefined values in modes 0 / 2 -- and a label outside [0, K).
+ * h * w <= 16384 (the channel is staged in LDS), H * W < 2^31, n <= 65535; out 4-byte, boxes 16-byte aligned. */
+int as_paste_masks(const float* src, const long long* labels, const float* boxes, void* out, int n, int K, int h, int w,
+                   int H, int W, int apply_sigmoid, int out_mode, float thr, as_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,133 @@
+"""Times the test-time post-processing of one image on both routes, in one process on one GPU:
+
+    multiclass_nms   1000 proposals x 20 classes, score_thr 0.05, IoU 0.5, 100 kept (the shipped VOC test config)
+    get_seg_masks    100 detections, 28 x 28 masks, a 1024 x 1024 image, threshold 0.5
+
+`device` = csrc/detect_post.hip (as_nms / as_paste_masks), `host` = the tensor-op route on the same device tensors
+(AS_POST_HOST=1: full IoU matrix + Python loop; sigmoid over all classes + grid_sample).  Every call is followed by a device
+synchronize; the figure is the median of --repeats calls after --warmup, the two routes alternating call by call.  Prints a markdown table (profiles/post_bench.md
+is this output) and checks that both routes return the same detections.
+
+    python tools/post_bench.py [--repeats 10] [--warmup 2] [--out profiles/post_bench.md]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from attentionshift_amd import inference as I      # noqa: E402
+
+HBM_PEAK = 8.0e12          # bytes / s, MI355X
+
+
+def _route(route):
+    if route == "host":
+        os.environ["AS_POST_HOST"] = "1"
+    else:
+        os.environ.pop("AS_POST_HOST", None)
+
+
+def both_routes(fn, repeats, warmup):
+    """-> {route: (median s, min s, last result)}; the routes alternate call by call, so that a drift of the box (other
+    tenants, allocator warm-up) falls on both alike."""
+    ts, out = {"device": [], "host": []}, {}
+    for r in range(warmup + repeats):
+        for route in ("device", "host"):
+            _route(route)
+            t0 = time.perf_counter()
+            out[route] = fn(route)
+            torch.cuda.synchronize()
+            if r >= warmup:
+                ts[route].append(time.perf_counter() - t0)
+    _route("device")
+    return {k: (statistics.median(v), min(v), out[k]) for k, v in ts.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a GPU"
+    torch.set_grad_enabled(False)
+    gen = torch.Generator().manual_seed(2)
+    n, K = 1000, 20
+    xy = torch.rand(n, 2, generator=gen) * 900
+    boxes = torch.cat((xy, xy + 10 + torch.rand(n, 2, generator=gen) * 200), 1)
+    per_class = (boxes[:, None, :] + torch.randn(n, K, 4, generator=gen) * 4).reshape(n, 4 * K).cuda()
+    scores = torch.softmax(torch.randn(n, K + 1, generator=gen) * 2.5, 1).cuda()
+    candidates = int((scores[:, :-1] > 0.05).sum())
+    nms = both_routes(lambda route: I.multiclass_nms(per_class, scores, 0.05, 0.5, 100), args.repeats, args.warmup)
+    (dd, ld), (dh, lh) = nms["device"][2], nms["host"][2]
+    assert torch.equal(ld, lh) and torch.equal(dd, dh), "the two NMS routes disagree"
+
+    m, H, W = 100, 1024, 1024
+    logits = (torch.randn(m, K, 28, 28, generator=gen) * 3).cuda()
+    bxy = torch.rand(m, 2, generator=gen) * 700
+    dets = torch.cat((bxy, bxy + 40 + torch.rand(m, 2, generator=gen) * 280, torch.rand(m, 1, generator=gen)), 1).cuda()
+    labels = torch.randint(0, K, (m,), generator=gen).cuda()
+    seg = both_routes(lambda route: I.get_seg_masks(logits, dets, labels, K, (H, W, 3), 1.0, True, 0.5), args.repeats, args.warmup)
+    sd, sh = (np.stack([x for s in r[2] for x in s]) for r in (seg["device"], seg["host"]))
+    differ = int((sd != sh).sum())
+    # the paste without the copy of the [m,H,W] bytes to the host and the per-class lists: the kernel against its floor
+    from attentionshift_amd import ops
+    box4 = dets[:, :4].contiguous()
+    paste = both_routes(lambda route: ops.paste_masks(logits, labels, box4, H, W, True, 1, 0.5) if route == "device"
+                        else _host_paste(logits, labels, box4, H, W), args.repeats, args.warmup)
+    t_k, t_h = paste["device"][0], paste["host"][0]
+    # ... and the kernel by itself: HIP events around back-to-back launches (no launch gap, no synchronize in the figure)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.repeats):
+        ops.paste_masks(logits, labels, box4, H, W, True, 1, 0.5)
+    e1.record()
+    torch.cuda.synchronize()
+    t_ev = e0.elapsed_time(e1) * 1e-3 / args.repeats
+
+    lines = [
+        "# Test-time post-processing: device kernels against the tensor-op route",
+        "",
+        f"`python tools/post_bench.py --repeats {args.repeats} --warmup {args.warmup}` on {torch.cuda.get_device_name(0)}; "
+        "wall time per call including the device synchronize, median (min) in ms.",
+        "",
+        "| stage | size | device (`csrc/detect_post.hip`) | host route (`AS_POST_HOST=1`) | host / device |",
+        "|---|---|---|---|---|",
+        f"| `multiclass_nms` | {n} proposals x {K} classes -> {candidates} candidates, 100 kept | "
+        f"{nms['device'][0] * 1e3:.3f} ({nms['device'][1] * 1e3:.3f}) | {nms['host'][0] * 1e3:.3f} ({nms['host'][1] * 1e3:.3f}) | "
+        f"{nms['host'][0] / nms['device'][0]:.1f} |",
+        f"| `get_seg_masks` (to numpy lists) | {m} x 28 x 28 -> {H} x {W} | "
+        f"{seg['device'][0] * 1e3:.3f} ({seg['device'][1] * 1e3:.3f}) | {seg['host'][0] * 1e3:.3f} ({seg['host'][1] * 1e3:.3f}) | "
+        f"{seg['host'][0] / seg['device'][0]:.1f} |",
+        f"| paste alone (result left on the device) | same | {t_k * 1e3:.3f} | {t_h * 1e3:.3f} | {t_h / t_k:.1f} |",
+        "",
+        f"Paste kernel: {m * H * W / 1e6:.1f} MB written in {t_k * 1e3:.3f} ms = {m * H * W / t_k / 1e12:.2f} TB/s = "
+        f"{100 * m * H * W / t_k / HBM_PEAK:.1f} % of the {HBM_PEAK / 1e12:.0f} TB/s HBM peak (launch and synchronize included); "
+        f"{t_ev * 1e3:.3f} ms per launch between HIP events over {args.repeats} back-to-back launches = "
+        f"{m * H * W / t_ev / 1e12:.2f} TB/s = {100 * m * H * W / t_ev / HBM_PEAK:.1f} % of peak.",
+        f"Both NMS routes return identical detections; the mask routes differ on {differ} of {sd.size} pixels.",
+    ]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+
+
+def _host_paste(logits, labels, dets, H, W):
+    """the tensor-op route up to the thresholded device tensor (what get_seg_masks does before its copy to the host)"""
+    probs = logits.sigmoid()
+    sel = probs[torch.arange(probs.shape[0], device=probs.device), labels][:, None]
+    return I.paste_masks(sel, dets[:, :4], H, W) >= 0.5          # (AS_POST_HOST=1 is set around this call)
+
+
+if __name__ == "__main__":
+    main()
