@@ -102,6 +102,11 @@ SIGNATURES = {
     "as_nms_workspace_bytes": (_c_size_t, [_c_int]),
     "as_nms": (_c_int, [_c_void_p, _c_int, _c_float, _c_int] + [_c_void_p] * 3 + [_c_size_t, _c_void_p]),
     "as_paste_masks": (_c_int, [_c_void_p] * 4 + [_c_int] * 8 + [_c_float, _c_void_p]),
+    "as_rle_tile": (_c_int, [_c_void_p] * 2),
+    "as_rle_workspace_bytes": (_c_size_t, [_c_int] * 3),
+    "as_rle_count": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
+    "as_rle_encode": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p] * 2 + [_c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_size_t,
+                               _c_void_p, _c_void_p]),
 }
 
 _lib = None

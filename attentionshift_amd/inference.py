@@ -9,6 +9,9 @@ csrc/detect_post.hip (ops.nms / ops.paste_masks), unless AS_POST_HOST=1 forces t
     paste_masks            fcn_mask_head._do_paste_mask: the RoI-sized mask resampled onto the image grid of its box
     get_seg_masks          mae_mask_head_pointSup.py:277-375: sigmoid, paste, threshold, per-class lists
     bbox2result            mmdet/core/bbox/transforms.py: per-class [n,5] arrays
+    rle_encode /           mmdet/core/mask/utils.py:36-63 (what mmdet/apis/test.py:60,100 does to every result):
+    encode_mask_results    pycocotools.mask.encode of every mask in Fortran order, restated (pycocotools is not needed);
+                           device tensors are encoded by the kernels of csrc/rle.hip (ops.rle_encode)
 """
 import os
 
@@ -101,15 +104,70 @@ def paste_masks(masks, boxes, img_h, img_w):
     return F.grid_sample(masks.float(), torch.stack([gx, gy], dim=3), align_corners=False)[:, 0]
 
 
+def _rle_counts_host(flat):
+    """flat: one mask's pixels in Fortran order (bool) -> its COCO `counts` string (rleEncode + rleToString)."""
+    a = flat.size
+    pos = np.flatnonzero(flat[1:] != flat[:-1]) + 1                        # the value changes ...
+    if a and flat[0]:
+        pos = np.concatenate(([0], pos))                                   # ... pixel 0 is one when it is set
+    cnts = np.diff(np.concatenate(([0], pos, [a]))).astype(np.int64)       # starts with a run of 0 (of length 0 then)
+    x = cnts.copy()
+    x[3:] -= cnts[1:-2]                                                    # i > 2: the difference to count i - 2
+    chars = np.zeros((x.size, 7), dtype=np.uint8)                          # a 32-bit count takes at most 7 groups
+    used = np.zeros((x.size, 7), dtype=bool)
+    alive = np.ones(x.size, dtype=bool)
+    for g in range(7):
+        c = x & 0x1f
+        x = x >> 5                                                         # arithmetic
+        more = np.where((c & 0x10) != 0, x != -1, x != 0)
+        chars[:, g] = (c | (more.astype(np.int64) << 5)) + 48
+        used[:, g] = alive
+        alive = alive & more
+    return chars[used].tobytes()
+
+
+def rle_encode(masks):
+    """masks [n,H,W] (tensor or numpy array; bool or uint8, any nonzero value counts as 1) -> list of n COCO RLE dicts
+    {'size': [H, W], 'counts': bytes}, what pycocotools.mask.encode returns for each mask in Fortran order: pixels column by
+    column, counts alternating from a run of 0, count i > 2 stored as its difference to count i - 2, 5-bit groups low first
+    with the continuation bit 0x20, + 48.  Device tensors run the kernels of csrc/rle.hip unless AS_POST_HOST=1."""
+    if torch.is_tensor(masks):
+        if masks.dim() != 3:
+            raise ValueError(f"rle_encode: masks must be [n, H, W], got {tuple(masks.shape)}")
+        H, W = int(masks.shape[1]), int(masks.shape[2])
+        if _on_device(masks):
+            if masks.dtype not in (torch.bool, torch.uint8):
+                masks = masks != 0
+            return [{"size": [H, W], "counts": c} for c in ops.rle_encode(masks.contiguous())]
+        masks = masks.cpu().numpy()
+    masks = np.asarray(masks)
+    if masks.ndim != 3:
+        raise ValueError(f"rle_encode: masks must be [n, H, W], got {masks.shape}")
+    n, H, W = masks.shape
+    flat = (masks != 0).transpose(0, 2, 1).reshape(n, H * W)
+    return [{"size": [H, W], "counts": _rle_counts_host(flat[i])} for i in range(n)]
+
+
+def encode_mask_results(mask_results):
+    """mmdet/core/mask/utils.py:36-63: per-class lists of [H,W] bitmap masks -> per-class lists of RLE dicts; the
+    (cls_segms, cls_mask_scores) tuple of mask scoring keeps its scores.  Entries that are RLE dicts already pass through."""
+    cls_segms = mask_results[0] if isinstance(mask_results, tuple) else mask_results
+    encoded = [[m if isinstance(m, dict) else rle_encode(np.asarray(m)[None])[0] for m in segms] for segms in cls_segms]
+    return (encoded, mask_results[1]) if isinstance(mask_results, tuple) else encoded
+
+
 def get_seg_masks(mask_pred, det_bboxes, det_labels, num_classes, ori_shape, scale_factor, rescale, mask_thr_binary=0.5,
-                  class_agnostic=False):
-    """mask_pred [n,K,h,w] logits -> list over classes of lists of bool numpy masks [H,W]."""
+                  class_agnostic=False, encode_rle=False):
+    """mask_pred [n,K,h,w] logits -> list over classes of lists of bool numpy masks [H,W]; with encode_rle, of their COCO
+    RLE dicts (encode_mask_results of the former; on the device route the masks are encoded there and never copied out)."""
+    if encode_rle and mask_thr_binary < 0:
+        raise ValueError("get_seg_masks: encode_rle needs binary masks (mask_thr_binary >= 0), not levels")
     cls_segms = [[] for _ in range(num_classes)]
     if mask_pred.shape[0] == 0:
         return cls_segms
     if _on_device(mask_pred):
         return _get_seg_masks_device(mask_pred, det_bboxes, det_labels, cls_segms, ori_shape, scale_factor, rescale,
-                                     mask_thr_binary, class_agnostic)
+                                     mask_thr_binary, class_agnostic, encode_rle)
     probs = mask_pred.sigmoid()
     boxes = det_bboxes[:, :4]
     if rescale:
@@ -126,13 +184,14 @@ def get_seg_masks(mask_pred, det_bboxes, det_labels, num_classes, ori_shape, sca
     full = full.cpu().numpy()
     for i, lab in enumerate(det_labels.tolist()):
         cls_segms[lab].append(full[i])
-    return cls_segms
+    return encode_mask_results(cls_segms) if encode_rle else cls_segms
 
 
 def _get_seg_masks_device(mask_pred, det_bboxes, det_labels, cls_segms, ori_shape, scale_factor, rescale, mask_thr_binary,
-                          class_agnostic):
+                          class_agnostic, encode_rle=False):
     """get_seg_masks on the device: sigmoid of the one class channel, paste and threshold in one kernel; the [n,H,W]
-    byte result is the only thing copied to the host."""
+    byte result is the only thing copied to the host -- or, with encode_rle, stays on the device and only its run-length
+    strings are."""
     boxes = det_bboxes[:, :4]
     if rescale:
         img_h, img_w = ori_shape[:2]
@@ -143,7 +202,7 @@ def _get_seg_masks_device(mask_pred, det_bboxes, det_labels, cls_segms, ori_shap
         img_h, img_w = int(np.round(ori_shape[0] * h_scale)), int(np.round(ori_shape[1] * w_scale))
     full = ops.paste_masks(mask_pred.float().contiguous(), None if class_agnostic else det_labels.long().contiguous(),
                            boxes.float().contiguous(), img_h, img_w, True, 1 if mask_thr_binary >= 0 else 2, mask_thr_binary)
-    full = full.cpu().numpy()
+    full = rle_encode(full) if encode_rle else full.cpu().numpy()
     for i, lab in enumerate(det_labels.tolist()):
         cls_segms[lab].append(full[i])
     return cls_segms

@@ -8,6 +8,7 @@ import os
 
 import threading
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1143,3 +1144,44 @@ def paste_masks(src, labels, boxes, H, W, apply_sigmoid, out_mode, thr=0.5):
         _lib.check(lib.as_paste_masks(_p(src), _p(labels), _p(boxes), _p(out), n, K, h, w, int(H), int(W),
                                       int(bool(apply_sigmoid)), int(out_mode), float(thr), _stream()), "as_paste_masks")
     return out
+
+
+def rle_tile():
+    """(rows per row segment, columns per workgroup) of the RLE kernels (csrc/rle.hip)."""
+    rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.load().as_rle_tile(ctypes.addressof(rows), ctypes.addressof(cols)), "as_rle_tile")
+    return rows.value, cols.value
+
+
+def rle_encode(masks):
+    """masks [n,H,W] bool or uint8 on the device (any nonzero byte counts as 1) -> list of n `bytes`: the COCO RLE
+    `counts` string of every mask in Fortran order (pycocotools' rleEncode + rleToString; as_rle_count / as_rle_encode).
+    One readback of the n run totals sizes the buffers (the output size is data dependent); the strings and their lengths
+    come back in one copy.  n <= 65535, H * W <= 2^31 - 1."""
+    lib = _lib.load()
+    _chk(masks)
+    if masks.dtype not in (torch.bool, torch.uint8):
+        raise AttnShiftError(f"rle_encode: masks must be bool or uint8, got {masks.dtype}")
+    if masks.dim() != 3:
+        raise AttnShiftError(f"rle_encode: masks must be [n, H, W], got {tuple(masks.shape)}")
+    n, H, W = masks.shape
+    if n == 0:
+        return []
+    if H * W == 0:
+        return [b"0"] * n                                   # rleEncode of no pixels: the single count 0
+    dev = masks.device
+    nbytes = lib.as_rle_workspace_bytes(n, H, W)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    totals = torch.empty(n, device=dev, dtype=torch.int32)
+    _lib.check(lib.as_rle_count(_p(masks), n, H, W, _p(totals), _p(ws), nbytes, _stream()), "as_rle_count")
+    tot = totals.cpu().numpy().astype(np.int64)            # the readback
+    runs = int(tot.sum())
+    pos = torch.empty(runs, device=dev, dtype=torch.int32)
+    cap = 7 * (runs + n)
+    out = torch.empty(8 * n + cap, device=dev, dtype=torch.uint8)      # [n uint64 lengths | the strings' slots]
+    _lib.check(lib.as_rle_encode(_p(masks), n, H, W, _p(totals), _p(ws), nbytes, _p(pos) if runs else 0, runs,
+                                 out.data_ptr() + 8 * n, cap, _p(out), _stream()), "as_rle_encode")
+    host = out.cpu().numpy()
+    lens = host[:8 * n].view(np.uint64).astype(np.int64)
+    starts = 8 * n + 7 * (np.cumsum(tot) - tot + np.arange(n))
+    return [host[a:a + l].tobytes() for a, l in zip(starts.tolist(), lens.tolist())]

@@ -976,8 +976,8 @@ class AttnShiftRoIHead(nn.Module):
     def simple_test(self, x, proposal_list, img_metas, proposals=None, rescale=False):
         """stdroi:3192-3221 + test_mixins.py:52-170, 262-340: per image, the box head on the proposals' RoI features ->
         softmax scores + decoded boxes -> class-aware NMS; then the mask head on the DETECTIONS' RoI features (the mask
-        extractor's 14x14 grid) -> pasted binary masks.  Returns [(bbox_results, segm_results)] per image, or
-        [bbox_results] without a mask head."""
+        extractor's 14x14 grid) -> pasted binary masks (their COCO RLE dicts with test_cfg.encode_rle).  Returns
+        [(bbox_results, segm_results)] per image, or [bbox_results] without a mask head."""
         from . import inference as I
         if not isinstance(self.bbox_head, nn.Module):
             raise RuntimeError("simple_test needs the box head built from its config (bbox_head with in_channels)")
@@ -1008,7 +1008,7 @@ class AttnShiftRoIHead(nn.Module):
             # the INPUT-scale boxes go in (test_mixins.py:293-331): get_seg_masks divides by scale_factor once itself
             segm = I.get_seg_masks(mask_pred, mboxes, labels, self.mask_head.num_classes, meta["ori_shape"],
                                    meta.get("scale_factor", 1.0), rescale, _get(cfg, "mask_thr_binary", 0.5),
-                                   self.mask_head.class_agnostic)
+                                   self.mask_head.class_agnostic, encode_rle=bool(_get(cfg, "encode_rle", False)))
             out.append((boxes_res, segm))
         return out
 

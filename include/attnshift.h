@@ -500,7 +500,7 @@ int as_chamfer_2d_bwd(const float* xyz1, const float* xyz2, const float* gdist1,
                       const int32_t* idx2, float* gxyz1, float* gxyz2, int B, int n, int m, as_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Part C -- test-time post-processing of the RoI head (csrc/detect_post.hip)
+ * Part C -- test-time post-processing of the RoI head (csrc/detect_post.hip, csrc/rle.hip)
  * ------------------------------------------------------------------------------------------- */
 
 /* Greedy NMS, the mmcv.ops.nms behind mmdet/core/post_processing/bbox_nms.py:84 (batched_nms; IoU without the +1 offset):
@@ -527,6 +527,33 @@ int as_nms(const float* boxes_sorted, int n, float iou_thr, int max_keep, long l
  * h * w <= 16384 (the channel is staged in LDS), H * W < 2^31, n <= 65535; out 4-byte, boxes 16-byte aligned. */
 int as_paste_masks(const float* src, const long long* labels, const float* boxes, void* out, int n, int K, int h, int w,
                    int H, int W, int apply_sigmoid, int out_mode, float thr, as_stream_t stream);
+
+/* COCO run-length encoding of test-time masks on the device (csrc/rle.hip): what mmdet/core/mask/utils.py:36-63
+ * (encode_mask_results, pycocotools.mask.encode of every mask in Fortran order) does on the host to every simple_test
+ * result (mmdet/apis/test.py:60,100), so that only the encoded strings leave the device.
+ *   masks [n,H,W] bytes, row-major, any alignment (as_paste_masks' mode 1 output); ANY NONZERO BYTE COUNTS AS 1.
+ * Pixels run column by column (p = x * H + y); the counts alternate between runs of 0 and 1 starting with a run of 0
+ * (T value changes -> T + 1 counts); count i is written as x = cnt[i] - cnt[i-2] for i > 2, else cnt[i], in 5-bit groups
+ * low first: c = x & 31, x >>= 5, continuation bit 0x20 unless the rest is the sign extension of bit 0x10, byte c + 48
+ * (rleEncode + rleToString; at most 7 bytes per count).
+ *
+ * as_rle_count: totals [n] uint32 = T of every mask (the output size is data dependent: the caller reads the totals back,
+ *   as it does as_nms' count), and the scanned cell offsets as_rle_encode needs, left in the workspace.
+ * as_rle_encode: the same masks, totals and workspace again.  pos: room for pos_capacity >= sum(T) uint32 (the change
+ *   positions, scratch; NULL allowed when pos_capacity = 0).  Mask d's string is written at str + 7 * (sum(T[0..d)) + d)
+ *   -- the room of its T + 1 counts -- and lens[d] (uint64) is its length; str_capacity >= 7 * (sum(T) + n) bytes.  Stores
+ *   past either capacity are dropped.  Deterministic: every position's place follows from the scan, no atomics.
+ * Workspace: as_rle_workspace_bytes(n, H, W) = 8 * (n + 1) + 5 * n * ceil(H / rows) * W bytes (0 when n, H or W <= 0),
+ *   8-byte aligned; totals 4-byte, lens 8-byte aligned.  as_rle_tile reports the tiling: rows per row segment (one wave)
+ *   and columns per workgroup.
+ * n == 0 or H * W == 0 returns 0 without a launch; H * W > 2^31 - 1 or n > 65535 is AS_E_UNSUPPORTED. */
+int as_rle_tile(int* rows_per_segment, int* cols_per_workgroup);
+size_t as_rle_workspace_bytes(int n, int H, int W);
+int as_rle_count(const void* masks, int n, int H, int W, uint32_t* totals, void* workspace, size_t workspace_bytes,
+                 as_stream_t stream);
+int as_rle_encode(const void* masks, int n, int H, int W, const uint32_t* totals, void* workspace, size_t workspace_bytes,
+                  uint32_t* pos, size_t pos_capacity, void* str, size_t str_capacity, unsigned long long* lens,
+                  as_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -2,6 +2,9 @@
 
     multiclass_nms   1000 proposals x 20 classes, score_thr 0.05, IoU 0.5, 100 kept (the shipped VOC test config)
     get_seg_masks    100 detections, 28 x 28 masks, a 1024 x 1024 image, threshold 0.5
+    ... to COCO RLE  the same masks as run-length strings: get_seg_masks(encode_rle=True), encoded on the device
+                     (csrc/rle.hip), against the bitmap get_seg_masks + encode_mask_results on the host; and the
+                     encode kernels alone
 
 `device` = csrc/detect_post.hip (as_nms / as_paste_masks), `host` = the tensor-op route on the same device tensors
 (AS_POST_HOST=1: full IoU matrix + Python loop; sigmoid over all classes + grid_sample).  Every call is followed by a device
@@ -35,13 +38,15 @@ def _route(route):
         os.environ.pop("AS_POST_HOST", None)
 
 
-def both_routes(fn, repeats, warmup):
+def both_routes(fn, repeats, warmup, switch=True):
     """-> {route: (median s, min s, last result)}; the routes alternate call by call, so that a drift of the box (other
-    tenants, allocator warm-up) falls on both alike."""
+    tenants, allocator warm-up) falls on both alike.  switch=False leaves AS_POST_HOST alone: fn(route) tells the two
+    apart itself."""
     ts, out = {"device": [], "host": []}, {}
     for r in range(warmup + repeats):
         for route in ("device", "host"):
-            _route(route)
+            if switch:
+                _route(route)
             t0 = time.perf_counter()
             out[route] = fn(route)
             torch.cuda.synchronize()
@@ -49,6 +54,37 @@ def both_routes(fn, repeats, warmup):
                 ts[route].append(time.perf_counter() - t0)
     _route("device")
     return {k: (statistics.median(v), min(v), out[k]) for k, v in ts.items()}
+
+
+def rle_kernels_alone(masks, repeats):
+    """-> seconds per encode (as_rle_count + as_rle_encode back to back) between HIP events: no readback, no allocation"""
+    from attentionshift_amd import _lib
+    lib = _lib.load()
+    n, H, W = masks.shape
+    nbytes = lib.as_rle_workspace_bytes(n, H, W)
+    ws = torch.empty(nbytes, device=masks.device, dtype=torch.uint8)
+    totals = torch.empty(n, device=masks.device, dtype=torch.int32)
+    st = torch.cuda.current_stream().cuda_stream
+
+    def count():
+        _lib.check(lib.as_rle_count(masks.data_ptr(), n, H, W, totals.data_ptr(), ws.data_ptr(), nbytes, st), "as_rle_count")
+    count()
+    runs = int(totals.sum())
+    pos = torch.empty(max(runs, 1), device=masks.device, dtype=torch.int32)
+    out = torch.empty(8 * n + 7 * (runs + n), device=masks.device, dtype=torch.uint8)
+
+    def encode():
+        _lib.check(lib.as_rle_encode(masks.data_ptr(), n, H, W, totals.data_ptr(), ws.data_ptr(), nbytes, pos.data_ptr(), runs,
+                                     out.data_ptr() + 8 * n, 7 * (runs + n), out.data_ptr(), st), "as_rle_encode")
+    encode()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(repeats):
+        count()
+        encode()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e-3 / repeats, runs, out.numel()
 
 
 def main():
@@ -92,6 +128,16 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     t_ev = e0.elapsed_time(e1) * 1e-3 / args.repeats
+    # the masks as COCO RLE: encoded on the device (only the strings leave it) against the bitmaps copied out and encoded
+    # on the host -- both start from the same paste kernel, so the strings must be equal
+    seg_args = (logits, dets, labels, K, (H, W, 3), 1.0, True, 0.5)
+    rle = both_routes(lambda route: I.get_seg_masks(*seg_args, encode_rle=True) if route == "device"
+                      else I.encode_mask_results(I.get_seg_masks(*seg_args)), args.repeats, args.warmup, switch=False)
+    assert rle["device"][2] == rle["host"][2], "the device and the host encoding disagree"
+    rle_bytes = sum(len(r["counts"]) for c in rle["device"][2] for r in c)
+    pasted = ops.paste_masks(logits, labels, box4, H, W, True, 1, 0.5)
+    t_rle, runs, copied = rle_kernels_alone(pasted, args.repeats)
+    assert seg["device"][0] > rle["device"][0], "encoding on the device is slower than copying the bitmaps out"
 
     lines = [
         "# Test-time post-processing: device kernels against the tensor-op route",
@@ -114,6 +160,25 @@ def main():
         f"{t_ev * 1e3:.3f} ms per launch between HIP events over {args.repeats} back-to-back launches = "
         f"{m * H * W / t_ev / 1e12:.2f} TB/s = {100 * m * H * W / t_ev / HBM_PEAK:.1f} % of peak.",
         f"Both NMS routes return identical detections; the mask routes differ on {differ} of {sd.size} pixels.",
+        "",
+        "## The masks as COCO RLE (`csrc/rle.hip`)",
+        "",
+        "Both columns paste on the device; they alternate call by call like the routes above.",
+        "",
+        "| stage | encoded on the device: `get_seg_masks(encode_rle=True)` | bitmap `get_seg_masks` + `encode_mask_results` on the host |",
+        "|---|---|---|",
+        f"| {m} masks {H} x {W} to per-class lists of RLE dicts | {rle['device'][0] * 1e3:.3f} ({rle['device'][1] * 1e3:.3f}) | "
+        f"{rle['host'][0] * 1e3:.3f} ({rle['host'][1] * 1e3:.3f}) |",
+        "",
+        f"Bitmap `get_seg_masks` alone (the device column of the first table, no encoding at all): {seg['device'][0] * 1e3:.3f} ms; "
+        f"with the encoding on the device: {rle['device'][0] * 1e3:.3f} ms = {seg['device'][0] / rle['device'][0]:.1f} x faster, "
+        f"{rle['host'][0] / rle['device'][0]:.0f} x faster than copying out and encoding on the host.",
+        f"Encode kernels (`as_rle_count` + `as_rle_encode`, five launches): {t_rle * 1e3:.3f} ms between HIP events over "
+        f"{args.repeats} back-to-back encodes; they read the masks twice, {2 * m * H * W / 1e6:.1f} MB = "
+        f"{2 * m * H * W / t_rle / 1e12:.2f} TB/s = {100 * 2 * m * H * W / t_rle / HBM_PEAK:.1f} % of the HBM peak "
+        "(the 105 MB fit the Infinity Cache).  "
+        f"{runs} value changes in all; {copied} bytes are copied to the host ({rle_bytes} bytes of strings) instead of {m * H * W}.",
+        "The device and the host encoding return identical strings.",
     ]
     text = "\n".join(lines) + "\n"
     print(text)
