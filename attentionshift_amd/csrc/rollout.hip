@@ -104,6 +104,8 @@ __global__ __launch_bounds__(RO_NT) void attn_mean_rows_kernel(const T* __restri
 //   * Q fragments of the next block are prefetched into registers while the current block is computed (bf16);
 //   * the four partial head sums are exchanged through a double-buffered 16 KiB LDS slab (one barrier per
 //     block) and every wave then owns ONE 32-row block of R for the second MFMA, so no final reduction.
+//     (fp32 with 16 heads: the K tile alone is 136 KiB, so the slab is single-buffered there -- xbufs == 1 -- at the
+//     price of a second barrier per block; 139264 + 2 * 16384 B would exceed the 160 KiB of a workgroup.)
 // ---------------------------------------------------------------------------------------------------------
 template <typename T> struct Kj2 {           // bf16: unpadded 128-B rows, XOR-swizzled 16-B chunks; f32: padded
   static constexpr int PITCH = sizeof(T) == 2 ? 128 : (HD * 4 + 16);
@@ -119,14 +121,14 @@ __global__ __launch_bounds__(RO_NT) void rollout_step2_kernel(const T* __restric
                                                               const float* __restrict__ Rin, const T* __restrict__ rf_in,
                                                               float* __restrict__ Rout, T* __restrict__ rf_out,
                                                               float* __restrict__ part, int B, int N, int Npad, int h,
-                                                              int Trows, int nsplit) {
+                                                              int Trows, int nsplit, int xbufs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool PREFETCH = sizeof(T) == 2;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, half = lane >> 5;
   const int j0 = blockIdx.x * 32, b = blockIdx.y, split = blockIdx.z;
   char* kj = smem;
-  float4* xchg = reinterpret_cast<float4*>(smem + (size_t)h * 32 * Kj2<T>::PITCH);    // [2][4 waves][4][64]
+  float4* xchg = reinterpret_cast<float4*>(smem + (size_t)h * 32 * Kj2<T>::PITCH);    // [xbufs][4 waves][4][64]
 
   {  // stage K rows j0..j0+31 of every head
     constexpr int CPR = HD * (int)sizeof(T) / 16;
@@ -213,7 +215,7 @@ __global__ __launch_bounds__(RO_NT) void rollout_step2_kernel(const T* __restric
       }
     }
     // publish this wave's partial head sum
-    float4* slab = xchg + (size_t)((kb - kb0) & 1) * 4 * 4 * 64;
+    float4* slab = xchg + (size_t)(xbufs == 2 ? (kb - kb0) & 1 : 0) * 4 * 4 * 64;
 #pragma unroll
     for (int g = 0; g < 4; ++g)
       slab[(wave * 4 + g) * 64 + lane] = make_float4(pbar[4 * g], pbar[4 * g + 1], pbar[4 * g + 2], pbar[4 * g + 3]);
@@ -239,6 +241,7 @@ __global__ __launch_bounds__(RO_NT) void rollout_step2_kernel(const T* __restric
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) acc = mma32(cur.fr[s2], fp[s2], acc);
     }
+    if (xbufs == 1) __syncthreads();                     // single slab: everyone has read it before the next block's writes
   }
 
   if (own_rows) {
@@ -744,14 +747,16 @@ int launch_rollout_step2(const void* q, const void* k, const float* lse, const f
   const int Npad = as_round_up(N, 64);
   const int hpw = as_ceil_div(h, 4);
   dim3 grid(as_ceil_div(N, 32), B, nsplit);
-  const size_t lds = (size_t)h * 32 * Kj2<T>::PITCH + 2 * 4 * 4 * 64 * sizeof(float4);
+  const size_t kbytes = (size_t)h * 32 * Kj2<T>::PITCH, slab = 4 * 4 * 64 * sizeof(float4);
+  const int xbufs = kbytes + 2 * slab <= 160 * 1024 ? 2 : 1;     // fp32, h = 16: one exchange slab (see rollout_step2_kernel)
+  const size_t lds = kbytes + xbufs * slab;
   AS_REQUIRE(lds <= 160 * 1024, AS_E_UNSUPPORTED, "rollout_step: LDS %zu B exceeds 160 KiB (h=%d)", lds, h);
 #define AS_RO2(HPW)                                                                                            \
   do {                                                                                                         \
     (void)hipFuncSetAttribute((const void*)rollout_step2_kernel<T, HPW>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                               (int)lds);                                                                       \
     hipLaunchKernelGGL((rollout_step2_kernel<T, HPW>), grid, dim3(RO_NT), lds, s, (const T*)q, (const T*)k, lse, Rin, \
-                       (const T*)rf_in, Rout, (T*)rf_out, part, B, N, Npad, h, Trows, nsplit);                 \
+                       (const T*)rf_in, Rout, (T*)rf_out, part, B, N, Npad, h, Trows, nsplit, xbufs);          \
   } while (0)
   if (sizeof(T) == 2 && h % R4_HPG == 0 && part != nullptr && nsplit == R4_MAXPARTS && !rollout_force_v3()) {
     // bf16, heads in groups of four: streamed-operand kernel; `nsplit` here only says that the workspace holds

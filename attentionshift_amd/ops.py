@@ -542,12 +542,13 @@ def attn_mean_rows(state, row0, nrows):
     return out
 
 
-def rollout_rows(states, num_point_tokens, rows=None):
+def rollout_rows(states, num_point_tokens, rows=None, use_workspace=True):
     """Row-sliced attention roll-out over `states` (ordered bottom -> top, as the reference's
     attns[-cam_layer:]).  Returns [B, Lc, T, N] fp32; index k = product of the top k+1 layers
     (reference stdroi:1257-1272 + the row slice of :2272).  `rows` (long [B, G], indices into the T point-token rows):
     only those rows are pushed through the layers below the top one -> [B, Lc, G, N] (a row of the product depends on
-    that row of R alone, so the values are the ones the full roll-out holds)."""
+    that row of R alone, so the values are the ones the full roll-out holds).  use_workspace=False hands as_rollout_step
+    no workspace: every step runs unsplit (one workgroup per 32-column block and image)."""
     lib = _lib.load()
     top = states[-1]
     T = int(num_point_tokens)
@@ -567,7 +568,7 @@ def rollout_rows(states, num_point_tokens, rows=None):
             rf = torch.empty(nbytes, device=dev, dtype=torch.uint8)
             _lib.check(lib.as_rollout_pack(_p(R), _p(rf), top.B, top.N, T, dt, _stream()), "as_rollout_pack")
     outs.append(R)
-    wbytes = lib.as_rollout_step_workspace_bytes(top.B, top.N, T) if lower else 0
+    wbytes = lib.as_rollout_step_workspace_bytes(top.B, top.N, T) if (lower and use_workspace) else 0
     ws = torch.empty(wbytes, device=dev, dtype=torch.uint8) if wbytes else None     # contraction-split partials
     for n, st in enumerate(lower):
         Rn = torch.empty_like(R)

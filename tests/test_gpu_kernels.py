@@ -1293,8 +1293,9 @@ def test_swin_block_matches_reference(ops, golden, tag, dtype, tol):
 @pytest.mark.parametrize("with_delta", [True, False])
 def test_add_layernorm_autograd_matches_torch(ops, M, D, dtype, tol, with_delta):
     """autograd.AddLayerNormFn (as_add_layernorm forward, as_add_layernorm_bwd backward) vs torch autograd in fp64 of
-    x_out = x + delta, y = LayerNorm(x_out): gradients of x, delta, gamma, beta when BOTH outputs are used, more rows than
-    workgroups (grid-stride partials) and fewer than one workgroup."""
+    x_out = x + delta, y = LayerNorm(x_out): gradients of x, delta, gamma, beta when BOTH outputs are used, with many workgroup
+    partials (M = 1030: 258 workgroups, each row loop runs once) and with two workgroups (M = 5).  More rows than the 1024
+    workgroups cover in one pass (M > 4096, the grid-stride loop's second pass): tests/test_gpu_layernorm.py."""
     from attentionshift_amd import autograd as AG
     g = torch.Generator().manual_seed(M + D)
     x = torch.randn(M, D, generator=g) * 2 + 0.5
@@ -1627,12 +1628,9 @@ def _ref_small_attn(qkv):
     return (p @ v).permute(0, 2, 1, 3).flatten(2)
 
 
-@pytest.mark.parametrize("N,dtype,tol", [(50, torch.float32, 2e-5), (197, torch.float32, 2e-5), (50, torch.bfloat16, 2e-2),
-                                         (300, torch.bfloat16, 2e-2), (1, torch.float32, 2e-5)])
-def test_small_attention_forward_backward(ops, N, dtype, tol):
-    """as_small_attn_fwd / _bwd (head dim 32, packed qkv) vs fp64 softmax attention and its autograd gradient."""
+def _check_small_attention(ops, N, h, dtype, tol):
     gen = torch.Generator().manual_seed(N)
-    Bp, h = 5, 8
+    Bp = 5
     qkv = (torch.randn(Bp, N, 3, h, 32, generator=gen) * 1.5).to(dtype)
     out, lse = ops.small_attention_fwd(dev(qkv))
     with torch.enable_grad():
@@ -1648,6 +1646,24 @@ def test_small_attention_forward_backward(ops, N, dtype, tol):
     dqkv = ops.small_attention_bwd(dev(qkv), out, dev(g), lse)
     gr = float(x.grad.abs().max())
     assert float((dqkv.double().cpu() - x.grad).abs().max()) < (5 * tol) * gr
+
+
+@pytest.mark.parametrize("N,dtype,tol", [(50, torch.float32, 2e-5), (197, torch.float32, 2e-5), (50, torch.bfloat16, 2e-2),
+                                         (300, torch.bfloat16, 2e-2), (1, torch.float32, 2e-5),
+                                         (32, torch.float32, 2e-5), (33, torch.float32, 2e-5), (64, torch.float32, 2e-5),
+                                         (32, torch.bfloat16, 2e-2), (33, torch.bfloat16, 2e-2), (64, torch.bfloat16, 2e-2)])
+def test_small_attention_forward_backward(ops, N, dtype, tol):
+    """as_small_attn_fwd / _bwd (head dim 32, packed qkv) vs fp64 softmax attention and its autograd gradient.  N = 32, 33, 64:
+    exactly one 32-row block, one row past it, exactly two."""
+    _check_small_attention(ops, N, 8, dtype, tol)
+
+
+@pytest.mark.parametrize("h", [1, 3])
+@pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-5), (torch.bfloat16, 2e-2)])
+def test_small_attention_with_a_wave_task_count_that_is_no_multiple_of_four(ops, h, dtype, tol):
+    """N = 50 with h heads: 2 h wave tasks per image (two 32-row blocks x h heads) = 2 and 6, no multiple of the four waves of a
+    workgroup, so the last workgroup's early-return waves run.  Same reference and tolerances."""
+    _check_small_attention(ops, 50, h, dtype, tol)
 
 
 def test_mae_box_head_matches_tensor_op_decoder():
