@@ -107,7 +107,15 @@ SIGNATURES = {
     "as_rle_count": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     "as_rle_encode": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p] * 2 + [_c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_size_t,
                                _c_void_p, _c_void_p]),
+    "as_rpn_candidates_workspace_bytes": (_c_size_t, [_c_int] * 2),
+    "as_rpn_candidates": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p] * 2 + [_c_int, _c_float, _c_void_p, _c_float, _c_int]
+                          + [_c_void_p] * 7 + [_c_size_t, _c_void_p]),
 }
+
+
+class RpnLevel(ctypes.Structure):
+    """as_rpn_level of include/attnshift.h"""
+    _fields_ = [("cls", _c_void_p), ("reg", _c_void_p), ("H", _c_int), ("W", _c_int), ("stride_x", _c_int), ("stride_y", _c_int)]
 
 _lib = None
 

@@ -12,6 +12,9 @@ csrc/detect_post.hip (ops.nms / ops.paste_masks), unless AS_POST_HOST=1 forces t
     rle_encode /           mmdet/core/mask/utils.py:36-63 (what mmdet/apis/test.py:60,100 does to every result):
     encode_mask_results    pycocotools.mask.encode of every mask in Fortran order, restated (pycocotools is not needed);
                            device tensors are encoded by the kernels of csrc/rle.hip (ops.rle_encode)
+    rpn_candidates /       mmdet/models/dense_heads/rpn_head.py:82-236 (RPNHead._get_bboxes): per-level top nms_pre by
+    rpn_nms /              logit, anchors (anchor_generator.py:142-270), delta2bbox, minimum size, then mmcv's batched_nms
+    rpn_proposals          with the level as the class; device tensors run csrc/rpn.hip (ops.rpn_candidates) and as_nms
 """
 import os
 
@@ -35,18 +38,7 @@ def nms(boxes, scores, iou_threshold, max_keep=-1):
     if boxes.numel() == 0:
         return torch.zeros(0, dtype=torch.long, device=boxes.device)
     order = scores.argsort(descending=True, stable=True)
-    if _on_device(boxes):
-        return order[ops.nms(boxes[order].contiguous().float(), iou_threshold, max_keep)]
-    iou = bbox_overlaps(boxes[order], boxes[order], eps=1e-12).cpu()
-    n = iou.shape[0]
-    alive = torch.ones(n, dtype=torch.bool)
-    keep = []
-    for i in range(n):
-        if alive[i]:
-            keep.append(i)
-            alive &= ~(iou[i] > iou_threshold)
-            alive[i] = False
-    return order[torch.tensor(keep, dtype=torch.long, device=boxes.device)]
+    return order[_nms_in_order(boxes[order], iou_threshold, max_keep)]
 
 
 def multiclass_nms(multi_bboxes, multi_scores, score_thr, iou_threshold, max_num=-1):
@@ -68,6 +60,109 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, iou_threshold, max_num
     if max_num > 0:
         keep = keep[:max_num]
     return torch.cat((bboxes[keep], scores[keep, None]), dim=1), labels[keep]
+
+
+def _nms_in_order(boxes_sorted, iou_threshold, max_keep=-1):
+    """Greedy NMS over boxes that are in visiting order already -> kept positions, ascending (device route: at most
+    max_keep of them when max_keep > 0)."""
+    n = boxes_sorted.shape[0]
+    if n == 0:
+        return torch.zeros(0, dtype=torch.long, device=boxes_sorted.device)
+    if _on_device(boxes_sorted):
+        return ops.nms(boxes_sorted.contiguous().float(), iou_threshold, max_keep)
+    iou = bbox_overlaps(boxes_sorted, boxes_sorted, eps=1e-12).cpu()
+    alive = torch.ones(n, dtype=torch.bool)
+    keep = []
+    for i in range(n):
+        if alive[i]:
+            keep.append(i)
+            alive &= ~(iou[i] > iou_threshold)
+            alive[i] = False
+    return torch.tensor(keep, dtype=torch.long, device=boxes_sorted.device)
+
+
+def _rpn_candidates_host(cls_scores, bbox_preds, base_anchors, strides, img_shapes, nms_pre, min_bbox_size, means, stds):
+    """The definition of rpn_candidates in tensor ops (any device)."""
+    from .rpn import grid_anchors
+    L, B, dev = len(cls_scores), cls_scores[0].shape[0], cls_scores[0].device
+    C = ops.rpn_candidate_count(cls_scores, nms_pre)
+    out_box, out_nms = cls_scores[0].new_zeros(B, C, 4), cls_scores[0].new_zeros(B, C, 4)
+    out_score = cls_scores[0].new_zeros(B, C)
+    out_level = torch.zeros(B, C, dtype=torch.int32, device=dev)
+    out_index = torch.zeros(B, C, dtype=torch.int32, device=dev)
+    out_count = torch.zeros(B, dtype=torch.int32, device=dev)
+    anchors = [grid_anchors(base_anchors[l].to(dev), cls_scores[l].shape[2:], strides[l]) for l in range(L)]
+    for b in range(B):
+        logits, deltas, anch, levels, index = [], [], [], [], []
+        for l in range(L):
+            lg = cls_scores[l][b].permute(1, 2, 0).reshape(-1)
+            dl = bbox_preds[l][b].permute(1, 2, 0).reshape(-1, 4)
+            idx = torch.arange(lg.numel(), device=dev)
+            if 0 < nms_pre < lg.numel():
+                idx = torch.sort(lg, descending=True, stable=True)[1][:nms_pre]
+            logits.append(lg[idx]); deltas.append(dl[idx]); anch.append(anchors[l][idx]); index.append(idx)
+            levels.append(torch.full_like(idx, l))
+        logits, deltas, anch, levels, index = (torch.cat(v) for v in (logits, deltas, anch, levels, index))
+        order = torch.sort(logits, descending=True, stable=True)[1]        # ties keep (level, index) order
+        logits, deltas, anch, levels, index = (v[order] for v in (logits, deltas, anch, levels, index))
+        boxes = delta2bbox(anch, deltas, means, stds, max_shape=img_shapes[b])
+        scores = 1 / (1 + torch.exp(-logits))
+        if min_bbox_size > 0:
+            ok = ((boxes[:, 2] - boxes[:, 0]) >= min_bbox_size) & ((boxes[:, 3] - boxes[:, 1]) >= min_bbox_size)
+            boxes, scores, levels, index = boxes[ok], scores[ok], levels[ok], index[ok]
+        m = boxes.shape[0]
+        if m:
+            out_box[b, :m], out_score[b, :m] = boxes, scores
+            out_nms[b, :m] = boxes + (levels.to(boxes) * (boxes.max() + 1))[:, None]
+            out_level[b, :m], out_index[b, :m] = levels.to(torch.int32), index.to(torch.int32)
+        out_count[b] = m
+    return out_box, out_nms, out_score, out_level, out_index, out_count
+
+
+def rpn_candidates(cls_scores, bbox_preds, base_anchors, strides, img_shapes, nms_pre, min_bbox_size=0, means=(0., 0., 0., 0.),
+                   stds=(1., 1., 1., 1.)):
+    """The RPN's test-time stage before NMS (mmdet/models/dense_heads/rpn_head.py:82-231).  cls_scores[l] [B,A,H_l,W_l],
+    bbox_preds[l] [B,4A,H_l,W_l] fp32, base_anchors [L,A,4], strides[l] = (sx, sy), img_shapes[b] = (h, w[, c]).
+    Candidate i = (y * W_l + x) * A + a of level l has the logit cls[b,a,y,x] and the anchor base[l][a] + its grid shift.
+    Everywhere the order is (logit descending, level ascending, i ascending; -0.0 == +0.0, NaN first).  Every (image,
+    level) keeps its first min(nms_pre, n_l) candidates (nms_pre <= 0: all); they are decoded (delta2bbox clipped to the
+    image, score = sigmoid of the logit), those narrower or lower than min_bbox_size (when > 0) are dropped, and the rest
+    returned per image in that order:
+        (cand_box [B,C,4], cand_nms_box [B,C,4], cand_score [B,C], cand_level [B,C] int32, cand_index [B,C] int32,
+         cand_count [B] int32),  C = sum_l min(nms_pre, n_l);  rows past an image's count carry no meaning.
+    cand_nms_box = box + level * (M + 1), M the image's largest remaining coordinate (batched_nms with the level as the
+    class).  Device tensors run csrc/rpn.hip (ops.rpn_candidates) unless AS_POST_HOST=1; CPU tensors the tensor ops."""
+    cls_scores = [c.float().contiguous() for c in cls_scores]
+    bbox_preds = [r.float().contiguous() for r in bbox_preds]
+    strides = [(s, s) if isinstance(s, int) else (int(s[0]), int(s[1])) for s in strides]
+    if not torch.is_tensor(base_anchors):
+        base_anchors = torch.stack(list(base_anchors))
+    if _on_device(cls_scores[0]):
+        return ops.rpn_candidates(cls_scores, bbox_preds, base_anchors, strides, img_shapes, nms_pre, min_bbox_size, means, stds)
+    return _rpn_candidates_host(cls_scores, bbox_preds, base_anchors.float(), strides, img_shapes, nms_pre, min_bbox_size, means,
+                                stds)
+
+
+def rpn_nms(cand_box, cand_nms_box, cand_score, iou_threshold, max_per_img=-1):
+    """One image's candidates in their order -> proposals [m,5]: greedy NMS over the level-offset boxes, the first
+    max_per_img kept (all when <= 0), the un-offset boxes and the score; and the kept positions."""
+    keep = _nms_in_order(cand_nms_box, iou_threshold, max_per_img)
+    if max_per_img > 0:
+        keep = keep[:max_per_img]
+    return torch.cat((cand_box[keep], cand_score[keep, None]), dim=1), keep
+
+
+def rpn_proposals(cls_scores, bbox_preds, base_anchors, strides, img_shapes, nms_pre, max_per_img, iou_threshold, min_bbox_size=0,
+                  means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.)):
+    """RPNHead._get_bboxes (mmdet/models/dense_heads/rpn_head.py:82-236): rpn_candidates, then per image mmcv's batched_nms
+    with the level as the class at iou_threshold and the first max_per_img survivors -> list of [m,5] (x1,y1,x2,y2,score),
+    [0,5] when nothing survives.  On the device route nothing is read back before NMS unless min_bbox_size > 0 (the
+    counts, once for all images)."""
+    box, nms_box, score, _, _, count = rpn_candidates(cls_scores, bbox_preds, base_anchors, strides, img_shapes, nms_pre,
+                                                      min_bbox_size, means, stds)
+    B, C = score.shape
+    counts = [C] * B if min_bbox_size <= 0 else count.tolist()
+    return [rpn_nms(box[b, :m], nms_box[b, :m], score[b, :m], iou_threshold, max_per_img)[0] for b, m in enumerate(counts)]
 
 
 def get_det_bboxes(rois, cls_score, bbox_pred, img_shape, scale_factor, rescale, score_thr=0.05, iou_threshold=0.5,

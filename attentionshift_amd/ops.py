@@ -1186,3 +1186,72 @@ def rle_encode(masks):
     lens = host[:8 * n].view(np.uint64).astype(np.int64)
     starts = 8 * n + 7 * (np.cumsum(tot) - tot + np.arange(n))
     return [host[a:a + l].tobytes() for a, l in zip(starts.tolist(), lens.tolist())]
+
+
+# ------------------------------------------------------------------------------------------------
+# Part C: RPN proposal candidates (csrc/rpn.hip)
+# ------------------------------------------------------------------------------------------------
+_IMG_SHAPES = {}
+
+
+def _img_shapes(img_shapes, device):
+    """[B,2] fp32 (h, w) on `device`, uploaded once per distinct list (a pageable copy waits for the stream)"""
+    key = (tuple((float(s[0]), float(s[1])) for s in img_shapes), device)
+    t = _IMG_SHAPES.get(key)
+    if t is None:
+        if len(_IMG_SHAPES) > 256:
+            _IMG_SHAPES.clear()
+        t = _IMG_SHAPES[key] = torch.tensor(key[0], dtype=torch.float32).reshape(-1, 2).to(device)
+    return t
+
+
+def rpn_candidate_count(cls_scores, nms_pre):
+    """C = sum over the levels of min(nms_pre, A * H * W) (nms_pre <= 0: the whole level)"""
+    ns = [int(c.shape[1] * c.shape[2] * c.shape[3]) for c in cls_scores]
+    return sum(n if nms_pre <= 0 else min(int(nms_pre), n) for n in ns)
+
+
+def rpn_candidates(cls_scores, bbox_preds, base_anchors, strides, img_shapes, nms_pre, min_bbox_size=0, means=(0., 0., 0., 0.),
+                   stds=(1., 1., 1., 1.), wh_ratio_clip=16 / 1000):
+    """cls_scores[l] [B,A,H_l,W_l], bbox_preds[l] [B,4A,H_l,W_l] fp32 on the device, base_anchors [L,A,4], strides[l] =
+    (sx, sy) or one int, img_shapes[b] = (h, w[, c]) -> (cand_box [B,C,4], cand_nms_box [B,C,4], cand_score [B,C],
+    cand_level [B,C] int32, cand_index [B,C] int32, cand_count [B] int32): the survivors of every image in the order (logit
+    descending, level, index), decoded, with the boxes offset by level for as_nms (as_rpn_candidates).  Nothing is read
+    back: with min_bbox_size <= 0 every count is C, otherwise cand_count tells how many rows of an image are written."""
+    lib = _lib.load()
+    L = len(cls_scores)
+    if L == 0 or len(bbox_preds) != L or len(strides) != L:
+        raise AttnShiftError("rpn_candidates: cls_scores, bbox_preds and strides need one entry per level (at least one)")
+    _chk(*cls_scores, *bbox_preds, dtype=torch.float32)
+    B, A = int(cls_scores[0].shape[0]), int(cls_scores[0].shape[1])
+    for c, r in zip(cls_scores, bbox_preds):
+        if c.dim() != 4 or r.dim() != 4 or c.shape[0] != B or c.shape[1] != A or tuple(r.shape) != (B, 4 * A, c.shape[2], c.shape[3]):
+            raise AttnShiftError("rpn_candidates: cls_scores[l] [B,A,H,W] and bbox_preds[l] [B,4A,H,W] with one B and A")
+    if len(img_shapes) != B:
+        raise AttnShiftError(f"rpn_candidates: {len(img_shapes)} image shapes for {B} images")
+    dev = cls_scores[0].device
+    base = base_anchors.to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(base.shape) != (L, A, 4):
+        raise AttnShiftError(f"rpn_candidates: base_anchors must be [{L}, {A}, 4], got {tuple(base.shape)}")
+    levels = (_lib.RpnLevel * L)()
+    for l, (c, r, s) in enumerate(zip(cls_scores, bbox_preds, strides)):
+        sx, sy = (s, s) if isinstance(s, int) else (s[0], s[1])
+        levels[l] = _lib.RpnLevel(_p(c), _p(r), int(c.shape[2]), int(c.shape[3]), int(sx), int(sy))
+    C = rpn_candidate_count(cls_scores, nms_pre)
+    shapes = _img_shapes(img_shapes, dev)
+    ms = (ctypes.c_float * 8)(*[float(v) for v in means], *[float(v) for v in stds])
+    cand_box = torch.empty(B, C, 4, device=dev, dtype=torch.float32)
+    cand_nms_box = torch.empty(B, C, 4, device=dev, dtype=torch.float32)
+    cand_score = torch.empty(B, C, device=dev, dtype=torch.float32)
+    cand_level = torch.empty(B, C, device=dev, dtype=torch.int32)
+    cand_index = torch.empty(B, C, device=dev, dtype=torch.int32)
+    cand_count = torch.empty(B, device=dev, dtype=torch.int32)
+    if B == 0:
+        return cand_box, cand_nms_box, cand_score, cand_level, cand_index, cand_count
+    nbytes = lib.as_rpn_candidates_workspace_bytes(B, C)
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    _lib.check(lib.as_rpn_candidates(ctypes.addressof(levels), L, B, A, _p(base), _p(shapes), int(nms_pre), float(min_bbox_size),
+                                     ctypes.addressof(ms), abs(float(np.log(wh_ratio_clip))), C, _p(cand_box), _p(cand_nms_box),
+                                     _p(cand_score), _p(cand_level), _p(cand_index), _p(cand_count), _p(ws), nbytes, _stream()),
+               "as_rpn_candidates")
+    return cand_box, cand_nms_box, cand_score, cand_level, cand_index, cand_count

@@ -97,9 +97,15 @@ def build_head(cfg):
     return HEADS.build(cfg)
 
 
+# registered here only: these have no losses, and mmdet's own classes of the same names train with theirs
+NOT_INTO_MMDET = ("RPNHead",)
+
+
 def register_into_mmdet():
-    """Drop-in: register the MI355X classes under the reference's names in mmdet's registries."""
+    """Drop-in: register the MI355X classes under the reference's names in mmdet's registries (all but NOT_INTO_MMDET)."""
     from mmdet.models.builder import BACKBONES as MM_BACKBONES, HEADS as MM_HEADS  # noqa: raises if absent
     for reg, mine in ((MM_BACKBONES, BACKBONES), (MM_HEADS, HEADS)):
         for name, cls in mine.module_dict.items():
+            if name in NOT_INTO_MMDET:
+                continue
             reg.register_module(name=name, force=True, module=cls)

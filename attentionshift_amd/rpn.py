@@ -1,0 +1,124 @@
+"""The proposal generator at test time: mmdet's anchor generator and RPN head, restated.
+
+    AnchorGenerator   mmdet/core/anchor/anchor_generator.py:142-270 (gen_single_level_base_anchors with centre offset 0,
+                      scale-major; single_level_grid_anchors).  Only the base anchors [L,A,4] reach the device route:
+                      csrc/rpn.hip computes an anchor from (level, index); grid_anchors serves the tensor-op route and tests.
+    RPNHead           mmdet/models/dense_heads/rpn_head.py:16-47, 82-236 + rpn_test_mixin.py simple_test_rpn + AnchorHead.
+                      get_bboxes: the 3x3 convolution, ReLU, the two 1x1 convolutions (through torch: plumbing), then
+                      inference.rpn_proposals.  Parameter names are the reference's (rpn_conv, rpn_cls, rpn_reg), so its
+                      checkpoints load.  The RPN LOSSES (anchor targets, MaxIoUAssigner, RandomSampler, loss_cls / loss_bbox)
+                      are not part of this build: loss_cls and loss_bbox are accepted and unused.
+"""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import inference
+from .registry import HEADS
+
+
+def _pair(v):
+    return (int(v), int(v)) if not isinstance(v, (tuple, list)) else (int(v[0]), int(v[1]))
+
+
+def grid_anchors(base_anchors, featmap_size, stride):
+    """base_anchors [A,4], (H, W), (sx, sy) -> [H * W * A, 4]: row (y * W + x) * A + a = base[a] + (x sx, y sy, x sx, y sy)"""
+    H, W = int(featmap_size[0]), int(featmap_size[1])
+    sx, sy = _pair(stride)
+    shift_x = torch.arange(0, W, device=base_anchors.device) * sx
+    shift_y = torch.arange(0, H, device=base_anchors.device) * sy
+    xx, yy = shift_x.repeat(H), shift_y.view(-1, 1).repeat(1, W).view(-1)
+    shifts = torch.stack([xx, yy, xx, yy], dim=-1).type_as(base_anchors)
+    return (base_anchors[None, :, :] + shifts[:, None, :]).view(-1, 4)
+
+
+class AnchorGenerator:
+    def __init__(self, scales, ratios, strides, base_sizes=None, type=None):
+        self.strides = [_pair(s) for s in strides]
+        self.base_sizes = [min(s) for s in self.strides] if base_sizes is None else list(base_sizes)
+        if len(self.base_sizes) != len(self.strides):
+            raise ValueError(f"AnchorGenerator: {len(self.strides)} strides but {len(self.base_sizes)} base sizes")
+        self.scales, self.ratios = torch.Tensor(scales), torch.Tensor(ratios)
+        self.base_anchors = [self._base(b) for b in self.base_sizes]
+
+    def _base(self, base_size):
+        h_ratios = torch.sqrt(self.ratios)
+        w_ratios = 1 / h_ratios
+        ws = (base_size * w_ratios[:, None] * self.scales[None, :]).view(-1)
+        hs = (base_size * h_ratios[:, None] * self.scales[None, :]).view(-1)
+        return torch.stack([0 - 0.5 * ws, 0 - 0.5 * hs, 0 + 0.5 * ws, 0 + 0.5 * hs], dim=-1)
+
+    @property
+    def num_levels(self):
+        return len(self.strides)
+
+    @property
+    def num_base_anchors(self):
+        return [b.size(0) for b in self.base_anchors]
+
+    def grid_anchors(self, featmap_sizes, device="cpu"):
+        """(tests and the tensor-op route only) -> per level [H * W * A, 4]"""
+        if len(featmap_sizes) != self.num_levels:
+            raise ValueError(f"AnchorGenerator: {len(featmap_sizes)} feature maps for {self.num_levels} levels")
+        return [grid_anchors(b.to(device), fs, s) for b, fs, s in zip(self.base_anchors, featmap_sizes, self.strides)]
+
+
+@HEADS.register_module()
+class RPNHead(nn.Module):
+    def __init__(self, in_channels, feat_channels=256, anchor_generator=None, bbox_coder=None, loss_cls=None, loss_bbox=None,
+                 train_cfg=None, test_cfg=None, **unused):
+        super().__init__()
+        ag = dict(anchor_generator or dict(scales=[8], ratios=[0.5, 1.0, 2.0], strides=[4, 8, 16, 32, 64]))
+        if ag.pop("type", "AnchorGenerator") != "AnchorGenerator":
+            raise ValueError("RPNHead: only AnchorGenerator anchors")
+        self.anchor_generator = AnchorGenerator(**ag)
+        if len(set(self.anchor_generator.num_base_anchors)) != 1:
+            raise ValueError("RPNHead: every level needs the same number of base anchors")
+        self.num_anchors = self.anchor_generator.num_base_anchors[0]
+        bc = dict(bbox_coder or {})
+        if bc.get("type", "DeltaXYWHBBoxCoder") != "DeltaXYWHBBoxCoder":
+            raise ValueError("RPNHead: only DeltaXYWHBBoxCoder")
+        self.target_means = tuple(float(v) for v in bc.get("target_means", (0., 0., 0., 0.)))
+        self.target_stds = tuple(float(v) for v in bc.get("target_stds", (1., 1., 1., 1.)))
+        if loss_cls is not None and not loss_cls.get("use_sigmoid", False):
+            raise ValueError("RPNHead: the softmax (two-channel) objectness of loss_cls.use_sigmoid=False is not built")
+        self.in_channels, self.feat_channels = in_channels, feat_channels
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        self.rpn_conv = nn.Conv2d(in_channels, feat_channels, 3, padding=1)
+        self.rpn_cls = nn.Conv2d(feat_channels, self.num_anchors, 1)
+        self.rpn_reg = nn.Conv2d(feat_channels, self.num_anchors * 4, 1)
+        self.register_buffer("base_anchors", torch.stack(self.anchor_generator.base_anchors), persistent=False)
+        self.init_weights()
+
+    def init_weights(self):
+        for m in (self.rpn_conv, self.rpn_cls, self.rpn_reg):
+            nn.init.normal_(m.weight, 0, 0.01)
+            nn.init.constant_(m.bias, 0)
+
+    def forward_single(self, x):
+        x = F.relu(self.rpn_conv(x), inplace=True)
+        return self.rpn_cls(x), self.rpn_reg(x)
+
+    def forward(self, feats):
+        """feats: per level [B, in_channels, H_l, W_l] -> (cls_scores, bbox_preds), two per-level lists"""
+        outs = [self.forward_single(x) for x in feats]
+        return [o[0] for o in outs], [o[1] for o in outs]
+
+    def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None):
+        """-> per image [m,5] proposals (x1, y1, x2, y2, score); cfg: nms_pre, max_per_img, nms.iou_threshold, min_bbox_size"""
+        cfg = self.test_cfg if cfg is None else cfg
+        if cfg is None:
+            raise ValueError("RPNHead.get_bboxes: no cfg and no test_cfg")
+        if len(cls_scores) != self.anchor_generator.num_levels:
+            raise ValueError(f"RPNHead: {len(cls_scores)} levels for {self.anchor_generator.num_levels} strides")
+        nms = cfg.get("nms") or dict(iou_threshold=cfg["nms_thr"])
+        max_per_img = cfg["max_per_img"] if "max_per_img" in cfg else cfg["max_num"]
+        return inference.rpn_proposals([c.detach() for c in cls_scores], [r.detach() for r in bbox_preds], self.base_anchors,
+                                       self.anchor_generator.strides, [m["img_shape"] for m in img_metas], cfg["nms_pre"],
+                                       max_per_img, nms["iou_threshold"], cfg.get("min_bbox_size", 0), self.target_means,
+                                       self.target_stds)
+
+    def simple_test_rpn(self, feats, img_metas):
+        """-> the proposal_list AttnShiftRoIHead.simple_test takes"""
+        cls_scores, bbox_preds = self.forward(feats)
+        return self.get_bboxes(cls_scores, bbox_preds, img_metas)

@@ -555,6 +555,41 @@ int as_rle_encode(const void* masks, int n, int H, int W, const uint32_t* totals
                   uint32_t* pos, size_t pos_capacity, void* str, size_t str_capacity, unsigned long long* lens,
                   as_stream_t stream);
 
+/* RPN proposal candidates (csrc/rpn.hip): everything mmdet/models/dense_heads/rpn_head.py:82-236 (RPNHead._get_bboxes) does
+ * before its batched_nms -- per-level top-k (:162-169), the anchors of mmdet/core/anchor/anchor_generator.py:142-270, the
+ * decode of mmdet/core/bbox/coder/delta_xywh_bbox_coder.py:134-237, the minimum-size filter (:221-231) -- and the class
+ * offset of mmcv.ops.batched_nms with the level as the class, in three launches for all B images and L levels.
+ *   levels [L]: a HOST array of level descriptors, L <= 8: cls = cls_scores[l] [B,A,H,W] fp32, reg = bbox_preds[l]
+ *     [B,4A,H,W] fp32 (device pointers), the anchor strides in pixels.
+ *   base_anchors [L,A,4] fp32 and img_shapes [B,2] fp32 = (h, w) of every image are device arrays; means_stds is a HOST
+ *     array of 8 floats (the 4 means, then the 4 stds); max_ratio = |log(wh_ratio_clip)|.
+ * Candidate i = (y * W + x) * A + a of level l has the logit cls[b,a,y,x], the deltas reg[b,4a..4a+3,y,x] and the anchor
+ * base_anchors[l][a] + (x * stride_x, y * stride_y, x * stride_x, y * stride_y); no anchor tensor is written.  The total
+ * order is (logit descending, level ascending, i ascending), -0.0 == +0.0, any NaN above +inf.  Every (image, level) keeps
+ * its first min(nms_pre, n_l) candidates of that order (nms_pre <= 0: all n_l = A * H * W); C = the sum of these over the
+ * levels, passed in and checked.  The survivors of an image are decoded (score = 1 / (1 + exp(-logit)); every step but exp
+ * rounds as the ATen ops do), those with w or h below min_bbox_size (when > 0) are dropped, and the rest are written in
+ * the total order:
+ *   cand_box [B,C,4] fp32, cand_nms_box [B,C,4] fp32 = box + level * (M + 1) with M the largest coordinate of the image's
+ *   remaining boxes (as_nms' input), cand_score [B,C], cand_level [B,C] and cand_index [B,C] int32 (l and i),
+ *   cand_count [B] int32 (= C when min_bbox_size <= 0); rows past the count are not written.
+ * Limits: L <= 8, at most 2048 survivors per (image, level) (so nms_pre <= 2048 whenever a level is larger, C <= 16384),
+ *   n_l < 2^28, B <= 65535, stride * extent < 2^24; beyond them AS_E_UNSUPPORTED.  Selection reads every logit twice (a
+ *   histogram of the keys' first 11 bits, then one collecting pass; four times when more than 4096 keys share the first 11
+ *   bits of the k-th one: the radix select then goes on over the other bits), never sorts a level.
+ * Workspace: as_rpn_candidates_workspace_bytes(B, C) = 36 * B * C bytes (0 when B or C <= 0), 16-byte aligned like
+ *   cand_box and cand_nms_box.  B == 0 returns 0 without a launch. */
+typedef struct {
+  const float* cls;
+  const float* reg;
+  int H, W, stride_x, stride_y;
+} as_rpn_level;
+size_t as_rpn_candidates_workspace_bytes(int B, int C);
+int as_rpn_candidates(const as_rpn_level* levels, int L, int B, int A, const float* base_anchors, const float* img_shapes,
+                      int nms_pre, float min_bbox_size, const float* means_stds, float max_ratio, int C, float* cand_box,
+                      float* cand_nms_box, float* cand_score, int32_t* cand_level, int32_t* cand_index, int32_t* cand_count,
+                      void* workspace, size_t workspace_bytes, as_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,5 +16,6 @@ python tools/gen_golden_hungarian.py
 python tools/gen_golden_mae_heads.py
 python tools/gen_golden_mmdet_pure.py
 python tools/gen_golden_point_loss.py
+python tools/gen_golden_rpn.py                # rpn (anchors, RPNHead._get_bboxes)
 python tools/gen_golden_sampler.py
 ls -la tests/golden

@@ -5,6 +5,8 @@
     ... to COCO RLE  the same masks as run-length strings: get_seg_masks(encode_rle=True), encoded on the device
                      (csrc/rle.hip), against the bitmap get_seg_masks + encode_mask_results on the host; and the
                      encode kernels alone
+    rpn_proposals    one image's five levels at 1024 x 1024 (261 888 anchors), nms_pre 1000, max_per_img 1000, IoU 0.7 (the
+                     shipped test_cfg.rpn): csrc/rpn.hip + as_nms against the tensor-op route, and the stage before NMS alone
 
 `device` = csrc/detect_post.hip (as_nms / as_paste_masks), `host` = the tensor-op route on the same device tensors
 (AS_POST_HOST=1: full IoU matrix + Python loop; sigmoid over all classes + grid_sample).  Every call is followed by a device
@@ -139,6 +141,8 @@ def main():
     t_rle, runs, copied = rle_kernels_alone(pasted, args.repeats)
     assert seg["device"][0] > rle["device"][0], "encoding on the device is slower than copying the bitmaps out"
 
+    rpn_lines = rpn_leg(args, gen)
+
     lines = [
         "# Test-time post-processing: device kernels against the tensor-op route",
         "",
@@ -179,12 +183,79 @@ def main():
         "(the 105 MB fit the Infinity Cache).  "
         f"{runs} value changes in all; {copied} bytes are copied to the host ({rle_bytes} bytes of strings) instead of {m * H * W}.",
         "The device and the host encoding return identical strings.",
-    ]
+    ] + rpn_lines
     text = "\n".join(lines) + "\n"
     print(text)
     if args.out:
         with open(args.out, "w") as f:
             f.write(text)
+
+
+def _library_launches(fn):
+    """-> kernel launches of the library in one call of fn: as_rpn_candidates is three, as_nms two (csrc/rpn.hip,
+    csrc/detect_post.hip); counted through the wrappers that make them"""
+    from attentionshift_amd import ops
+    n = {"rpn": 0, "nms": 0}
+    real_rpn, real_nms = ops.rpn_candidates, ops.nms
+    ops.rpn_candidates = lambda *a, **k: (n.__setitem__("rpn", n["rpn"] + 1), real_rpn(*a, **k))[1]
+    ops.nms = lambda *a, **k: (n.__setitem__("nms", n["nms"] + 1), real_nms(*a, **k))[1]
+    try:
+        fn()
+    finally:
+        ops.rpn_candidates, ops.nms = real_rpn, real_nms
+    return 3 * n["rpn"] + 2 * n["nms"]
+
+
+def rpn_leg(args, gen):
+    """RPN proposals of one image at 1024 x 1024: five levels (256^2 ... 16^2 positions x 3 anchors = 261 888 anchors), the
+    shipped test_cfg.rpn (nms_pre 1000, max_per_img 1000, IoU 0.7), both routes on device tensors."""
+    from attentionshift_amd import ops
+    from attentionshift_amd.rpn import AnchorGenerator
+    ag = AnchorGenerator([8], [0.5, 1.0, 2.0], [4, 8, 16, 32, 64])
+    sizes = [1024 // s for s in (4, 8, 16, 32, 64)]
+    cls = [(torch.randn(1, 3, s, s, generator=gen) * 2).cuda() for s in sizes]
+    reg = [(torch.randn(1, 12, s, s, generator=gen) * 0.2).cuda() for s in sizes]
+    base, shapes = torch.stack(ag.base_anchors).cuda(), [(1024, 1024, 3)]
+    call = lambda route: I.rpn_proposals(cls, reg, base, ag.strides, shapes, 1000, 1000, 0.7)      # noqa: E731
+    res = both_routes(call, args.repeats, args.warmup)
+    pd, ph = res["device"][2][0], res["host"][2][0]
+    same = pd.shape == ph.shape and torch.allclose(pd, ph, rtol=1e-6, atol=1e-5)
+    cand = lambda route: I.rpn_candidates(cls, reg, base, ag.strides, shapes, 1000)                # noqa: E731
+    sel = both_routes(cand, args.repeats, args.warmup)
+    order_equal = torch.equal(sel["device"][2][3], sel["host"][2][3]) and torch.equal(sel["device"][2][4], sel["host"][2][4])
+    C = sel["device"][2][2].shape[1]
+    # the three kernels of as_rpn_candidates by themselves: HIP events around back-to-back calls (allocations included)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.repeats):
+        ops.rpn_candidates(cls, reg, base, ag.strides, shapes, 1000)
+    e1.record()
+    torch.cuda.synchronize()
+    t_ev = e0.elapsed_time(e1) * 1e-3 / args.repeats
+    kernels = _library_launches(lambda: call("device"))
+    logit_bytes = sum(c.numel() for c in cls) * 4
+    return [
+        "",
+        "## RPN proposals (`csrc/rpn.hip` + `as_nms`)",
+        "",
+        f"One image, five levels {' / '.join(f'{s}^2' for s in sizes)} x 3 anchors = {sum(3 * s * s for s in sizes)} anchors, "
+        f"`nms_pre` 1000, `max_per_img` 1000, IoU 0.7 -> {C} candidates, {pd.shape[0]} proposals; inputs on the device on both "
+        "routes, median (min) in ms.",
+        "",
+        "| stage | device (`csrc/rpn.hip`) | host route (`AS_POST_HOST=1`) | host / device |",
+        "|---|---|---|---|",
+        f"| `rpn_proposals` (selection, decode, level NMS, gather) | {res['device'][0] * 1e3:.3f} ({res['device'][1] * 1e3:.3f}) | "
+        f"{res['host'][0] * 1e3:.3f} ({res['host'][1] * 1e3:.3f}) | {res['host'][0] / res['device'][0]:.1f} |",
+        f"| `rpn_candidates` (everything before NMS) | {sel['device'][0] * 1e3:.3f} ({sel['device'][1] * 1e3:.3f}) | "
+        f"{sel['host'][0] * 1e3:.3f} ({sel['host'][1] * 1e3:.3f}) | {sel['host'][0] / sel['device'][0]:.1f} |",
+        "",
+        f"`as_rpn_candidates` (three launches) between HIP events over {args.repeats} back-to-back calls: {t_ev * 1e3:.3f} ms; it reads "
+        f"the {logit_bytes / 1e6:.2f} MB of logits twice.  Kernel launches per `rpn_proposals` call on the device route: "
+        f"{kernels} of the library (3 for the candidates + 2 per image for `as_nms`) + torch's gather of the kept rows (two index "
+        "selects and one concatenation per image).",
+        f"The two routes select the same candidates in the same order: {order_equal}; their proposals agree within rtol 1e-6 / atol 1e-5 "
+        f"(they differ in `exp` alone): {same}.",
+    ]
 
 
 def _host_paste(logits, labels, dets, H, W):
