@@ -10,8 +10,8 @@
     giou_loss                 mmdet/models/losses/iou_loss.py:87-102 + iou2d_calculator.py:127-158 (aligned GIoU, the
                               union and the enclosing area clamped to eps); the shipped config regresses DECODED boxes
                               with it (reg_decoded_bbox=True, GIoULoss weight 10, attnshift_voc12aug.py:110-114)
-IoU assignment and sampling are in attentionshift_amd.assign; test-time proposal generation is in attentionshift_amd.rpn (the
-RPN's losses are not part of this build).
+IoU assignment and sampling are in attentionshift_amd.assign; proposal generation is in attentionshift_amd.rpn, the RPN's
+anchor targets and losses in attentionshift_amd.rpn_train.
 """
 import math
 

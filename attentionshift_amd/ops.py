@@ -1255,3 +1255,92 @@ def rpn_candidates(cls_scores, bbox_preds, base_anchors, strides, img_shapes, nm
                                      _p(cand_score), _p(cand_level), _p(cand_index), _p(cand_count), _p(ws), nbytes, _stream()),
                "as_rpn_candidates")
     return cand_box, cand_nms_box, cand_score, cand_level, cand_index, cand_count
+
+
+# ------------------------------------------------------------------------------------------------
+# RPN training targets (csrc/rpn_train.hip)
+# ------------------------------------------------------------------------------------------------
+def _rpn_grid_levels(featmap_sizes, strides):
+    """the host array of as_rpn_level descriptors of a geometry (no tensors: cls / reg stay NULL)"""
+    L = len(featmap_sizes)
+    if L == 0 or len(strides) != L:
+        raise AttnShiftError("rpn targets: featmap_sizes and strides need one entry per level (at least one)")
+    levels = (_lib.RpnLevel * L)()
+    for l, (fs, s) in enumerate(zip(featmap_sizes, strides)):
+        sx, sy = (s, s) if isinstance(s, int) else (s[0], s[1])
+        levels[l] = _lib.RpnLevel(None, None, int(fs[0]), int(fs[1]), int(sx), int(sy))
+    return levels
+
+
+def rpn_assign(base_anchors, featmap_sizes, strides, gt_boxes, gt_offsets, sum_g, max_g, shapes, pos_iou_thr, neg_iou_thr,
+               min_pos_iou, match_low_quality, allowed_border, workspace=None):
+    """as_rpn_assign: base_anchors [L,A,4] fp32, gt_boxes [sum_g,4] fp32, gt_offsets [B+1] int32, shapes [B,4] int32 =
+    (pad_h, pad_w, img_h, img_w), all on the device -> (assigned [B,T] int32, max_iou [B,T] fp32, counts [B,2] int32,
+    workspace): -2 outside / -1 / 0 / box + 1 per anchor; the workspace (uint8, allocated here unless given) is what
+    rpn_sample reads.  Nothing is read back."""
+    lib = _lib.load()
+    _chk(base_anchors, gt_boxes, dtype=torch.float32)
+    _chk(gt_offsets, shapes, dtype=torch.int32)
+    L, A = int(base_anchors.shape[0]), int(base_anchors.shape[1])
+    B = int(shapes.shape[0])
+    if len(featmap_sizes) != L or tuple(base_anchors.shape) != (L, A, 4):
+        raise AttnShiftError(f"rpn_assign: base_anchors {tuple(base_anchors.shape)} for {len(featmap_sizes)} levels")
+    if gt_offsets.numel() != B + 1 or tuple(shapes.shape) != (B, 4) or tuple(gt_boxes.shape) != (int(sum_g), 4):
+        raise AttnShiftError("rpn_assign: gt_boxes [sum_g,4], gt_offsets [B+1], shapes [B,4]")
+    levels = _rpn_grid_levels(featmap_sizes, strides)
+    T = sum(A * int(fs[0]) * int(fs[1]) for fs in featmap_sizes)
+    dev = base_anchors.device
+    assigned = torch.empty(B, T, device=dev, dtype=torch.int32)
+    max_iou = torch.empty(B, T, device=dev, dtype=torch.float32)
+    counts = torch.empty(B, 2, device=dev, dtype=torch.int32)
+    nbytes = lib.as_rpn_assign_workspace_bytes(B, T, int(sum_g))
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8) if workspace is None else workspace
+    _chk(ws, dtype=torch.uint8)
+    if ws.numel() < nbytes:
+        raise AttnShiftError(f"rpn_assign: workspace of {ws.numel()} bytes, {nbytes} needed")
+    _lib.check(lib.as_rpn_assign(ctypes.addressof(levels), L, B, A, _p(base_anchors), _p(gt_boxes) if sum_g else 0, _p(gt_offsets),
+                                 int(sum_g), int(max_g), _p(shapes), float(pos_iou_thr), float(neg_iou_thr), float(min_pos_iou),
+                                 int(bool(match_low_quality)), int(allowed_border), _p(assigned), _p(max_iou), _p(counts), _p(ws),
+                                 nbytes, _stream()), "as_rpn_assign")
+    return assigned, max_iou, counts, ws
+
+
+def rpn_sample(assigned, plan, ranks, workspace, sum_g):
+    """as_rpn_sample: assigned [B,T] int32 and the workspace of rpn_assign, plan [B,4] int32 = (n_pos, all_pos, n_neg,
+    all_neg), ranks [B,2,num] int32 -> inds [B,2,num] int32: per image the sampled positives' and negatives' anchor indices
+    ascending, -1 past their number."""
+    lib = _lib.load()
+    _chk(assigned, plan, ranks, dtype=torch.int32)
+    _chk(workspace, dtype=torch.uint8)
+    B, T = assigned.shape
+    num = int(ranks.shape[2])
+    if tuple(plan.shape) != (B, 4) or tuple(ranks.shape) != (B, 2, num):
+        raise AttnShiftError("rpn_sample: plan [B,4], ranks [B,2,num]")
+    inds = torch.empty(B, 2, num, device=assigned.device, dtype=torch.int32)
+    _lib.check(lib.as_rpn_sample(B, T, int(sum_g), num, _p(assigned), _p(plan), _p(ranks), _p(workspace), workspace.numel(), _p(inds),
+                                 _stream()), "as_rpn_sample")
+    return inds
+
+
+def rpn_targets(base_anchors, featmap_sizes, strides, gt_boxes, gt_offsets, sum_g, assigned, inds, means=(0., 0., 0., 0.),
+                stds=(1., 1., 1., 1.)):
+    """as_rpn_targets: inds [B,2,num] of rpn_sample (its positives are read) -> (pos_gt [B,num] int32 = the assigned box
+    of every sampled positive, -1 past their number; pos_delta [B,num,4] fp32 = bbox2delta(anchor, box, means, stds))."""
+    lib = _lib.load()
+    _chk(base_anchors, gt_boxes, dtype=torch.float32)
+    _chk(gt_offsets, assigned, inds, dtype=torch.int32)
+    L, A = int(base_anchors.shape[0]), int(base_anchors.shape[1])
+    B, T = assigned.shape
+    num = int(inds.shape[2])
+    if tuple(inds.shape) != (B, 2, num) or gt_offsets.numel() != B + 1 or len(featmap_sizes) != L:
+        raise AttnShiftError("rpn_targets: inds [B,2,num], gt_offsets [B+1], one feature map size per level")
+    if T != sum(A * int(fs[0]) * int(fs[1]) for fs in featmap_sizes):
+        raise AttnShiftError("rpn_targets: assigned does not have the geometry's number of anchors")
+    levels = _rpn_grid_levels(featmap_sizes, strides)
+    ms = (ctypes.c_float * 8)(*[float(v) for v in means], *[float(v) for v in stds])
+    pos_gt = torch.empty(B, num, device=assigned.device, dtype=torch.int32)
+    pos_delta = torch.empty(B, num, 4, device=assigned.device, dtype=torch.float32)
+    _lib.check(lib.as_rpn_targets(ctypes.addressof(levels), L, B, A, _p(base_anchors), _p(gt_boxes) if sum_g else 0, _p(gt_offsets),
+                                  int(sum_g), _p(assigned), _p(inds), 2 * num, num, ctypes.addressof(ms), _p(pos_gt), _p(pos_delta),
+                                  _stream()), "as_rpn_targets")
+    return pos_gt, pos_delta

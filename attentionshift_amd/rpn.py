@@ -1,4 +1,4 @@
-"""The proposal generator at test time: mmdet's anchor generator and RPN head, restated.
+"""The proposal generator: mmdet's anchor generator and RPN head, restated.
 
     AnchorGenerator   mmdet/core/anchor/anchor_generator.py:142-270 (gen_single_level_base_anchors with centre offset 0,
                       scale-major; single_level_grid_anchors).  Only the base anchors [L,A,4] reach the device route:
@@ -6,14 +6,17 @@
     RPNHead           mmdet/models/dense_heads/rpn_head.py:16-47, 82-236 + rpn_test_mixin.py simple_test_rpn + AnchorHead.
                       get_bboxes: the 3x3 convolution, ReLU, the two 1x1 convolutions (through torch: plumbing), then
                       inference.rpn_proposals.  Parameter names are the reference's (rpn_conv, rpn_cls, rpn_reg), so its
-                      checkpoints load.  The RPN LOSSES (anchor targets, MaxIoUAssigner, RandomSampler, loss_cls / loss_bbox)
-                      are not part of this build: loss_cls and loss_bbox are accepted and unused.
+                      checkpoints load.
+    RPNHead.loss /    AnchorHead.loss (mmdet/models/dense_heads/anchor_head.py:425-493) as RPNHead.loss renames it
+    forward_train     (rpn_head.py:49-80) and BaseDenseHead.forward_train (base_dense_head.py:22-59): the anchor targets,
+                      MaxIoUAssigner, RandomSampler and the two losses are in rpn_train (device tensors: csrc/rpn_train.hip).
+                      Built: CrossEntropyLoss(use_sigmoid=True), L1Loss, reg_decoded_bbox=False; anything else raises in loss.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import inference
+from . import inference, rpn_train
 from .registry import HEADS
 
 
@@ -84,6 +87,8 @@ class RPNHead(nn.Module):
             raise ValueError("RPNHead: the softmax (two-channel) objectness of loss_cls.use_sigmoid=False is not built")
         self.in_channels, self.feat_channels = in_channels, feat_channels
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        self.loss_cls_cfg, self.loss_bbox_cfg = dict(loss_cls or {}), dict(loss_bbox or {})
+        self.reg_decoded_bbox = bool(unused.get("reg_decoded_bbox", False))
         self.rpn_conv = nn.Conv2d(in_channels, feat_channels, 3, padding=1)
         self.rpn_cls = nn.Conv2d(feat_channels, self.num_anchors, 1)
         self.rpn_reg = nn.Conv2d(feat_channels, self.num_anchors * 4, 1)
@@ -122,3 +127,50 @@ class RPNHead(nn.Module):
         """-> the proposal_list AttnShiftRoIHead.simple_test takes"""
         cls_scores, bbox_preds = self.forward(feats)
         return self.get_bboxes(cls_scores, bbox_preds, img_metas)
+
+    def _loss_settings(self):
+        """-> (assigner, sampler, allowed_border, pos_weight, loss_cls weight, loss_bbox weight); raises on what is not built"""
+        cfg = self.train_cfg
+        if cfg is None:
+            raise ValueError("RPNHead.loss: no train_cfg (assigner, sampler, allowed_border, pos_weight)")
+        lc, lb = self.loss_cls_cfg, self.loss_bbox_cfg
+        if lc.get("type", "CrossEntropyLoss") != "CrossEntropyLoss" or not lc.get("use_sigmoid", bool(not lc)) or \
+                lc.get("class_weight") is not None or lc.get("reduction", "mean") != "mean":
+            raise ValueError("RPNHead.loss: only CrossEntropyLoss(use_sigmoid=True) with the mean reduction is built")
+        if lb.get("type", "L1Loss") != "L1Loss" or lb.get("reduction", "mean") != "mean":
+            raise ValueError("RPNHead.loss: only L1Loss with the mean reduction is built")
+        if self.reg_decoded_bbox:
+            raise ValueError("RPNHead.loss: reg_decoded_bbox=True is not built")
+        sampler = dict(cfg.get("sampler") or {})
+        if sampler.get("type", "RandomSampler") != "RandomSampler" or sampler.get("add_gt_as_proposals", False):
+            raise ValueError("RPNHead.loss: only RandomSampler without added GT boxes is built")
+        return (dict(cfg.get("assigner") or {}), sampler, int(cfg.get("allowed_border", 0)), cfg.get("pos_weight", -1),
+                float(lc.get("loss_weight", 1.0)), float(lb.get("loss_weight", 1.0)))
+
+    def loss(self, cls_scores, bbox_preds, gt_bboxes, img_metas, gt_bboxes_ignore=None, generator=None):
+        """-> dict(loss_rpn_cls=[L tensors], loss_rpn_bbox=[L tensors]), or None when an image has no anchor inside
+        (anchor_head.py:353-354).  On the device route the one host sync is the readback of the [B,2] counts."""
+        assigner, sampler, border, pos_weight, w_cls, w_bbox = self._loss_settings()
+        if len(cls_scores) != self.anchor_generator.num_levels:
+            raise ValueError(f"RPNHead: {len(cls_scores)} levels for {self.anchor_generator.num_levels} strides")
+        sizes = [tuple(int(v) for v in c.shape[-2:]) for c in cls_scores]
+        strides = self.anchor_generator.strides
+        base = self.base_anchors.to(cls_scores[0].device)
+        rpn_train._check_assigner(assigner, gt_bboxes_ignore)
+        if not all(rpn_train.any_inside(self.anchor_generator.base_anchors, sizes, strides, m, border) for m in img_metas):
+            return None
+        asg = rpn_train.rpn_assign(base, sizes, strides, gt_bboxes, img_metas, assigner, border, gt_bboxes_ignore)
+        smp = rpn_train.rpn_sample(asg, sampler.get("num", 256), sampler.get("pos_fraction", 0.5), sampler.get("neg_pos_ub", -1),
+                                   generator)
+        _, pos_delta = rpn_train.rpn_targets(asg, smp, self.target_means, self.target_stds)
+        loss_cls, loss_bbox = rpn_train.rpn_loss(cls_scores, bbox_preds, asg, smp, pos_delta, pos_weight, w_cls, w_bbox)
+        return dict(loss_rpn_cls=list(loss_cls.unbind(0)), loss_rpn_bbox=list(loss_bbox.unbind(0)))
+
+    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, generator=None):
+        """One forward, the losses and, with a proposal_cfg, the proposals of the detached outputs -> losses, or
+        (losses, proposal_list).  gt_labels are not used (the RPN is class agnostic)."""
+        cls_scores, bbox_preds = self.forward(x)
+        losses = self.loss(cls_scores, bbox_preds, gt_bboxes, img_metas, gt_bboxes_ignore=gt_bboxes_ignore, generator=generator)
+        if proposal_cfg is None:
+            return losses
+        return losses, self.get_bboxes(cls_scores, bbox_preds, img_metas, cfg=proposal_cfg)

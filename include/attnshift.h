@@ -590,6 +590,56 @@ int as_rpn_candidates(const as_rpn_level* levels, int L, int B, int A, const flo
                       float* cand_nms_box, float* cand_score, int32_t* cand_level, int32_t* cand_index, int32_t* cand_count,
                       void* workspace, size_t workspace_bytes, as_stream_t stream);
 
+/* RPN training targets (csrc/rpn_train.hip): what AnchorHead._get_targets_single (mmdet/models/dense_heads/anchor_head.py:
+ * 175-271) does per image before the losses, for all B images and L levels, without an anchor tensor or an IoU matrix.
+ * Anchor t of an image is level l, i = (y * W_l + x) * A + a, t = offset_l + i, T = the sum of the levels' A * H * W (the
+ * order of as_rpn_candidates); its coordinates are base_anchors[l][a] + the grid shift.
+ *   levels [L]: a HOST array; only H, W and the strides are read (cls / reg may be NULL).  base_anchors [L,A,4] fp32,
+ *   gt_boxes [sum_g,4] fp32 (the boxes of image b are rows gt_offsets[b] .. gt_offsets[b+1]), gt_offsets [B+1] int32 and
+ *   shapes [B,4] int32 = (pad_h, pad_w, img_h, img_w) are DEVICE arrays; sum_g and max_g (the largest number of boxes of
+ *   one image) are what the host knows of the offsets.
+ *
+ * as_rpn_assign replaces AnchorGenerator.valid_flags (mmdet/core/anchor/anchor_generator.py:272-328), anchor_inside_flags
+ * (mmdet/core/anchor/utils.py:20-46), BboxOverlaps2D and MaxIoUAssigner.assign / assign_wrt_overlaps
+ * (mmdet/core/bbox/assigners/max_iou_assigner.py:93-212; gt_max_assign_all = True, no ignore boxes, a float neg_iou_thr):
+ *   an anchor is inside when x < min(ceil(pad_w / sx), W_l), y < min(ceil(pad_h / sy), H_l) and, with allowed_border >= 0,
+ *   x1, y1 >= -allowed_border, x2 < img_w + allowed_border, y2 < img_h + allowed_border.
+ *   assigned [B,T] int32: -2 outside; inside: -1, 0 where 0 <= max_iou < neg_iou_thr, argmax + 1 where max_iou >=
+ *     pos_iou_thr (ties to the lowest box), then with match_low_quality for g ascending g + 1 on every anchor whose IoU with
+ *     box g equals the box's maximum over the inside anchors when that maximum is >= min_pos_iou; an image without boxes: 0.
+ *   max_iou [B,T] fp32 (0 outside and without boxes), counts [B,2] int32 = (positives, negatives).
+ *   The IoU is inter / max((area_gt + area_anchor) - inter, 1e-6) with every step one correctly rounded fp32 operation; the
+ *   per-box maxima are combined by integer atomic max on the bits (IoUs are >= 0): all outputs are bitwise reproducible.
+ *   NaN coordinates do not fault; a NaN IoU compares false everywhere (it is never a maximum), which torch.max would propagate.
+ * Workspace: as_rpn_assign_workspace_bytes(B, T, sum_g) = 16 * ceil(sum_g / 4) + 8 * B * ceil(T / 256) bytes (0 when B or
+ *   T <= 0 or sum_g < 0), 16-byte aligned: the per-box maxima, then per 256 anchors the scanned (positive, negative) counts
+ *   that as_rpn_sample reads -- pass the SAME workspace there.
+ *
+ * as_rpn_sample replaces the index side of RandomSampler (mmdet/core/bbox/samplers/base_sampler.py:82-100, random_sampler.py:
+ * 61-79: gallery[perm] and .unique()): plan [B,4] int32 = (n_pos, all_pos, n_neg, all_neg) and ranks [B,2,num] int32
+ *   (positives, then negatives) are device arrays; set s of image b takes n anchors: the ranks[b,s,j]-th positive (assigned
+ *   > 0) / negative (assigned == 0) in anchor order, or with `all` the ranks 0 .. n-1.  inds [B,2,num] int32: the anchor
+ *   indices t ascending, -1 past n and for ranks outside the set.
+ *
+ * as_rpn_targets replaces pos_assigned_gt_inds and DeltaXYWHBBoxCoder.encode (mmdet/core/bbox/coder/delta_xywh_bbox_coder.py:
+ * 88-130, bbox2delta) of anchor_head.py:237-243: pos_inds rows of inds_stride int32 whose first num entries are anchor
+ *   indices or -1; pos_gt [B,num] int32 = assigned - 1 (-1 for no anchor), pos_delta [B,num,4] fp32 =
+ *   (((gx - px) / pw, (gy - py) / ph, log(gw / pw), log(gh / ph)) - means) / stds in that operation order (zeros for no
+ *   anchor); only logf may round differently from ATen.  means_stds is a HOST array of 8 floats.
+ *
+ * Limits: L <= 8, a level below 2^28 anchors, stride * extent < 2^24, at most 1024 boxes per image, num <= 2048,
+ *   B <= 65535; beyond them AS_E_UNSUPPORTED.  Boxes are assumed finite.  B == 0 returns 0 without a launch. */
+size_t as_rpn_assign_workspace_bytes(int B, int T, int sum_g);
+int as_rpn_assign(const as_rpn_level* levels, int L, int B, int A, const float* base_anchors, const float* gt_boxes,
+                  const int32_t* gt_offsets, int sum_g, int max_g, const int32_t* shapes, float pos_iou_thr, float neg_iou_thr,
+                  float min_pos_iou, int match_low_quality, int allowed_border, int32_t* assigned, float* max_iou,
+                  int32_t* counts, void* workspace, size_t workspace_bytes, as_stream_t stream);
+int as_rpn_sample(int B, int T, int sum_g, int num, const int32_t* assigned, const int32_t* plan, const int32_t* ranks,
+                  const void* workspace, size_t workspace_bytes, int32_t* inds, as_stream_t stream);
+int as_rpn_targets(const as_rpn_level* levels, int L, int B, int A, const float* base_anchors, const float* gt_boxes,
+                   const int32_t* gt_offsets, int sum_g, const int32_t* assigned, const int32_t* pos_inds, int inds_stride,
+                   int num, const float* means_stds, int32_t* pos_gt, float* pos_delta, as_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
