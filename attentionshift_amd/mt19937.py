@@ -5,7 +5,8 @@ reference-RNG mode make its draws ON THE DEVICE (csrc/mt19937.hip) and still con
     unpack_state(blob)        torch.get_rng_state() bytes -> int32[626] = mt state words [624], left, next
     pack_state(blob, compact) the same blob with the engine advanced to `compact` (for torch.set_rng_state)
     MT                        numpy restatement of the engine and of the two draw patterns (tests; documentation of
-                              what the kernels do): draw(), skip(m), randint_first(n, n_draw, k), randperm_first(n, k)
+                              what the kernels do): draw(), skip(m), randint_first(n, n_draw, k), randperm_first(n, k),
+                              sampler_draws(counts, num, k_pos, neg_pos_ub) = the RPN sampler's draws (rpn_train.sample_plan)
 
 Layout of the blob (CPUGeneratorImplState, aten/src/ATen/CPUGeneratorImpl.cpp): the legacy TH generator record -- uint64
 the_initial_seed, int left, int seeded, uint64 next, uint64 state[624] (one engine word each), double normal_x, normal_y,
@@ -58,17 +59,21 @@ class MT:
         return np.concatenate((self.st, np.array([self.left, self.next], dtype=np.uint32))).view(np.int32)
 
     def _refill(self):
-        s = [int(v) for v in self.st]
+        """next_state() in the kernels' three dependent levels: entries 0..226 need old words only, 227..453 the first
+        level, 454..622 the second; the last entry needs the new word 0."""
+        old = self.st.astype(np.uint32)
 
         def twist(u, v):
-            return (((u & 0x80000000) | (v & 0x7FFFFFFF)) >> 1) ^ (0x9908B0DF if v & 1 else 0)
+            return (((u & np.uint32(0x80000000)) | (v & np.uint32(0x7FFFFFFF))) >> np.uint32(1)) ^ \
+                np.where(v & np.uint32(1), np.uint32(0x9908B0DF), np.uint32(0))
 
-        for i in range(N - M):                                   # i + M is still old
-            s[i] = s[i + M] ^ twist(s[i], s[i + 1])
-        for i in range(N - M, N - 1):                            # i + M - N is already new
-            s[i] = s[i + M - N] ^ twist(s[i], s[i + 1])
-        s[N - 1] = s[M - 1] ^ twist(s[N - 1], s[0])
-        self.st = np.array(s, dtype=np.uint32)
+        new = np.empty(N, dtype=np.uint32)
+        tw = twist(old[:N - 1], old[1:])
+        new[:N - M] = old[M:] ^ tw[:N - M]
+        new[N - M:2 * (N - M)] = new[:N - M] ^ tw[N - M:2 * (N - M)]
+        new[2 * (N - M):N - 1] = new[N - M:N - 1 - (N - M)] ^ tw[2 * (N - M):]
+        new[N - 1] = new[M - 1] ^ twist(old[N - 1:], new[:1])[0]
+        self.st = new
         self.left, self.next = N, 0
 
     def draw(self):
@@ -84,11 +89,17 @@ class MT:
         return y & 0xFFFFFFFF
 
     def skip(self, m):
-        for _ in range(m):
-            self.left -= 1
-            if self.left == 0:
+        """m draws whose words nobody reads, a block at a time"""
+        while m > 0:
+            if self.left == 1:                                       # the word that refills does not decrement `left`
                 self._refill()
-            self.next += 1
+                c = min(m, N)
+                self.left -= c - 1
+            else:
+                c = min(m, self.left - 1)
+                self.left -= c
+            self.next += c
+            m -= c
 
     def randint_first(self, n, n_draw, k):
         """(torch.randint(n, (n_draw,)) % n)[:k]"""
@@ -104,3 +115,33 @@ class MT:
             moved[i], moved[z + i] = b, a
         self.skip(max(n - 1, 0) - min(k, max(n - 1, 0)))
         return [moved.get(i, i) for i in range(min(k, n))]
+
+    def sampler_draws(self, counts, num, k_pos, neg_pos_ub=-1):
+        """RandomSampler's draws for the RPN on this engine (= rpn_train.sample_plan with k_pos = int(num * pos_fraction);
+        what a device-side draw has to reproduce): counts = [(n_pos, n_neg)] per image in order -> (plan np.int32 [B,4] =
+        (n_pos sampled, all_pos, n_neg sampled, all_neg), ranks np.int32 [B,2,num] with the draws first and zeros after
+        them, flag).  A set that fits its quota is taken whole and consumes no word.  flag = 1: an image with a count
+        outside [0, 0xffffffff // 20) (torch.randperm's other algorithm); it consumes nothing and its plan is zeros."""
+        if not 0 <= k_pos <= num:
+            raise ValueError(f"sampler_draws: k_pos = {k_pos} outside [0, {num}]")
+        plan = np.zeros((len(counts), 4), dtype=np.int32)
+        ranks = np.zeros((len(counts), 2, num), dtype=np.int32)
+        flag, limit = 0, 0xFFFFFFFF // 20
+        for b, (n_pos, n_neg) in enumerate(counts):
+            n_pos, n_neg = int(n_pos), int(n_neg)
+            if not (0 <= n_pos < limit and 0 <= n_neg < limit):
+                flag |= 1
+                continue
+            all_pos = n_pos <= k_pos
+            n_ps = n_pos if all_pos else k_pos
+            if not all_pos:
+                ranks[b, 0, :n_ps] = self.randperm_first(n_pos, k_pos)
+            k_neg = num - n_ps
+            if neg_pos_ub >= 0:
+                k_neg = min(k_neg, int(neg_pos_ub * max(1, n_ps)))
+            all_neg = n_neg <= k_neg
+            n_ns = n_neg if all_neg else k_neg
+            if not all_neg:
+                ranks[b, 1, :n_ns] = self.randperm_first(n_neg, k_neg)
+            plan[b] = (n_ps, all_pos, n_ns, all_neg)
+        return plan, ranks, flag
