@@ -211,4 +211,35 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+// min / max that hand a NaN on, whichever argument holds it (fminf / fmaxf drop it)
+__device__ __forceinline__ float nan_max(float a, float b) { return (a != a || a > b) ? a : b; }
+__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || a < b) ? a : b; }
+
+// inclusive prefix sum over the 64 lanes of a wave (lane = threadIdx.x & 63); the exclusive form is wave_incl_scan(v, lane) - v
+template <typename T> __device__ __forceinline__ T wave_incl_scan(T v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T u = __shfl_up(v, o);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+
+// ascending bitonic sort of a[0..P) in LDS by a workgroup of NT threads, P a power of two >= 2; ends with a barrier
+template <typename T, int NT> __device__ __forceinline__ void bitonic_sort(T* a, int P, int tid) {
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < (P >> 1); t += NT) {
+        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+        const T x = a[lo], y = a[hi];
+        const bool asc = (lo & size) == 0;
+        if ((x > y) == asc) {
+          a[lo] = y;
+          a[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
 #endif

@@ -15,8 +15,6 @@
 namespace {
 
 // torch.max / torch.min / clamp propagate NaN (fmaxf / fminf drop it)
-__device__ __forceinline__ float nan_max(float a, float b) { return (a != a || a > b) ? a : b; }
-__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || a < b) ? a : b; }
 
 constexpr int NMS_WAVES = 4;          // column blocks per workgroup of the mask kernel
 

@@ -10,6 +10,7 @@
 #include <utility>
 #include "common.h"
 #include "gemm_epi.h"
+#include "lds_asm.h"
 
 namespace {
 
@@ -241,39 +242,7 @@ template <int WM, int WN = 2, int RI = 2, int KS = 2, int NJ = 2> struct GTile {
   static constexpr int LDS = NSTAGE * STAGE > EPI_BYTES ? NSTAGE * STAGE : EPI_BYTES;
 };
 
-typedef __attribute__((ext_vector_type(4))) unsigned g_u32x4;
-__device__ __forceinline__ unsigned g_lds_addr(const void* p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-template <int OFF> __device__ __forceinline__ void g_lds_read128(g_u32x4& dst, unsigned addr) {
-  // the immediate is 16 bits; the 96 KiB ring of the 256 x 256 tile crosses it in its last stage (one v_add there)
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr + (unsigned)(OFF & ~0xFFFF)), "n"(OFF & 0xFFFF));
-}
-template <int LEFT> __device__ __forceinline__ void g_lds_wait4(g_u32x4& a, g_u32x4& b, g_u32x4& c, g_u32x4& d) {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(LEFT));   // LDS returns in order
-  __builtin_amdgcn_sched_barrier(0);
-}
-template <int LEFT, int N> __device__ __forceinline__ void g_lds_waitn(g_u32x4* f) {
-  static_assert(N == 6 || N == 8, "128 x 64 wave tile: 4 + 2 fragments per k16 step; 128 x 128: 4 + 4");
-  if constexpr (N == 6)
-    asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]) : "n"(LEFT));
-  else
-    asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]) : "n"(LEFT));
-  __builtin_amdgcn_sched_barrier(0);
-}
-template <int... I, typename F> __device__ __forceinline__ void g_static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F> __device__ __forceinline__ void g_static_for(F&& f) {
-  g_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
-
-// swizzle of the 16-byte chunk index inside a tile row, so that each ds_read_b128 lane group (16 lanes: rows {0-3, 12-15,
-// 20-27} or {4-11, 16-19, 28-31} of a 32-row block, one chunk column) covers the 16 slots of a 256-byte bank row once:
-// 64-byte rows (4 chunks): chunk ^ ((row >> 2) & 3); 128-byte rows (8 chunks): chunk ^ (((row >> 1) & 3) | ((row >> 4) & 1) << 2)
-template <int KS> __device__ __forceinline__ int g_swz(int r) {
-  return KS == 2 ? ((r >> 2) & 3) : (((r >> 1) & 3) | (((r >> 4) & 1) << 2));
-}
+// hidden fragment reads, their waits, static_for and the chunk swizzle lds_swz_row<KS>: lds_asm.h
 
 template <int MODE, int WM, int WN, int RI, int KS, int NJ = 2>
 __global__ __launch_bounds__(64 * WM * WN, (WN == 4 || KS == 4) ? 1 : (WM == 2 && RI == 2 ? 3 : 2)) void gemm_glds_kernel(
@@ -313,12 +282,12 @@ __global__ __launch_bounds__(64 * WM * WN, (WN == 4 || KS == 4) ? 1 : (WM == 2 &
 #pragma unroll
   for (int j = 0; j < NAP; ++j) {
     const int r = (wave * NAP + j) * PROWS + lr;
-    srcA[j] = reinterpret_cast<const char*>(A + (size_t)min(m0 + r, M - 1) * K + kbeg) + (lc ^ g_swz<KS>(r)) * 16;
+    srcA[j] = reinterpret_cast<const char*>(A + (size_t)min(m0 + r, M - 1) * K + kbeg) + (lc ^ lds_swz_row<KS>(r)) * 16;
   }
 #pragma unroll
   for (int j = 0; j < NWP; ++j) {
     const int r = (wave * NWP + j) * PROWS + lr;
-    srcW[j] = reinterpret_cast<const char*>(W + (size_t)min(n0 + r, Nout - 1) * K + kbeg) + (lc ^ g_swz<KS>(r)) * 16;
+    srcW[j] = reinterpret_cast<const char*>(W + (size_t)min(n0 + r, Nout - 1) * K + kbeg) + (lc ^ lds_swz_row<KS>(r)) * 16;
   }
   auto stage = [&](int kt, int buf) {
     char* base = smem + buf * G_STAGE;
@@ -343,15 +312,15 @@ __global__ __launch_bounds__(64 * WM * WN, (WN == 4 || KS == 4) ? 1 : (WM == 2 &
 
   // per-lane fragment addresses (loop-invariant): [ks] for the A rows of block i = 0 and the W rows of block j = 0;
   // the second block (+32 rows = +2048 B) and the ring stage are immediates
-  const unsigned smem_base = g_lds_addr(smem);
+  const unsigned smem_base = lds_addr(smem);
   unsigned offA[KS], offW[KS];
   {
     const int ra = wm * (32 * RI) + li, rb = wn * (32 * NJ) + li;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int g = ks * 2 + half;
-      offA[ks] = smem_base + ra * ROWB + ((g ^ g_swz<KS>(ra)) << 4);
-      offW[ks] = smem_base + G_TILE_BYTES + rb * ROWB + ((g ^ g_swz<KS>(rb)) << 4);
+      offA[ks] = smem_base + ra * ROWB + ((g ^ lds_swz_row<KS>(ra)) << 4);
+      offW[ks] = smem_base + G_TILE_BYTES + rb * ROWB + ((g ^ lds_swz_row<KS>(rb)) << 4);
     }
   }
 
@@ -362,7 +331,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WN == 4 || KS == 4) ? 1 : (WM == 2 &
   for (int p_ = 1; p_ < NSTAGE - 1; ++p_)
     if (nk > p_) stage(p_, p_);
   for (int kt0 = 0; kt0 < nk; kt0 += NSTAGE) {
-    g_static_for<NSTAGE>([&](auto slot_c) {
+    static_for<NSTAGE>([&](auto slot_c) {
       constexpr int slot = decltype(slot_c)::value;
       const int kt = kt0 + slot;
       if (kt >= nk) return;
@@ -377,35 +346,34 @@ __global__ __launch_bounds__(64 * WM * WN, (WN == 4 || KS == 4) ? 1 : (WM == 2 &
       if (AS_GEMM_ABLATE != 4) __builtin_amdgcn_s_barrier();   // publishes stage kt; everyone is done reading stage kt-1
       if (AS_GEMM_ABLATE != 1 && kt + NSTAGE - 1 < nk) stage(kt + NSTAGE - 1, (slot + NSTAGE - 1) % NSTAGE);
       constexpr int NF = RI + NJ;                    // fragments per k16 step: RI of A, NJ of W
-      g_static_for<KS / 2>([&](auto kp_c) {          // pairs of k16 steps
+      static_for<KS / 2>([&](auto kp_c) {          // pairs of k16 steps
       constexpr int k0 = 2 * decltype(kp_c)::value;
-      g_u32x4 f[2 * NF];                             // [ks][A0 .. A(RI-1), W0, W1]
+      u32x4 f[2 * NF];                             // [ks][A0 .. A(RI-1), W0, W1]
       if (AS_GEMM_ABLATE == 3) {
 #pragma unroll
         for (int x = 0; x < 2 * NF; ++x) asm volatile("" : "=v"(f[x]));
       }
-      if (AS_GEMM_ABLATE != 3) g_static_for<2>([&](auto ks_c) {
+      if (AS_GEMM_ABLATE != 3) static_for<2>([&](auto ks_c) {
         constexpr int ks = decltype(ks_c)::value;
-        g_static_for<RI>([&](auto i_c) {
+        static_for<RI>([&](auto i_c) {
           constexpr int i = decltype(i_c)::value;
-          g_lds_read128<slot * G_STAGE + i * 32 * ROWB>(f[ks * NF + i], offA[k0 + ks]);
+          lds_read128_i<slot * G_STAGE + i * 32 * ROWB>(f[ks * NF + i], offA[k0 + ks]);
         });
-        g_static_for<NJ>([&](auto j_c) {
+        static_for<NJ>([&](auto j_c) {
           constexpr int j = decltype(j_c)::value;
-          g_lds_read128<slot * G_STAGE + j * 32 * ROWB>(f[ks * NF + RI + j], offW[k0 + ks]);
+          lds_read128_i<slot * G_STAGE + j * 32 * ROWB>(f[ks * NF + RI + j], offW[k0 + ks]);
         });
       });
       // the first half's MFMAs start as soon as ITS fragments are back; the second half's reads finish under them
-      g_static_for<2>([&](auto ks_c) {
+      static_for<2>([&](auto ks_c) {
         constexpr int ks = decltype(ks_c)::value;
         if (AS_GEMM_ABLATE != 3) {
-          if constexpr (RI == 2 && NJ == 2) {
-            if (ks == 0) g_lds_wait4<4>(f[0], f[1], f[2], f[3]);
-            else g_lds_wait4<0>(f[4], f[5], f[6], f[7]);
-          } else {
-            if (ks == 0) g_lds_waitn<NF, NF>(&f[0]);
-            else g_lds_waitn<0, NF>(&f[NF]);
-          }
+          static_assert(NF == 4 || NF == 6 || NF == 8, "fragments per k16 step: 2 + 2, 4 + 2 (128 x 64 wave tile) or 4 + 4");
+          constexpr int LEFT = ks == 0 ? NF : 0;         // LDS returns in order
+          u32x4* const p = &f[ks * NF];
+          if constexpr (NF == 4) lds_wait<LEFT>(p[0], p[1], p[2], p[3]);
+          else if constexpr (NF == 6) lds_wait<LEFT>(p[0], p[1], p[2], p[3], p[4], p[5]);
+          else lds_wait<LEFT>(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7]);
         }
         if (AS_GEMM_ABLATE == 2) return;
 #pragma unroll

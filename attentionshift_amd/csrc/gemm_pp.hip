@@ -26,6 +26,7 @@
 #include <utility>
 #include "common.h"
 #include "gemm_epi.h"
+#include "lds_asm.h"
 
 #ifndef AS_PP_PRIO
 #define AS_PP_PRIO 1     // s_setprio: 0 none, 1 raised around the MFMA cluster, 2 raised in the load segment
@@ -47,7 +48,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned pp_u32x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 pp_bf16x2;
 
 struct PPEpi {
@@ -64,41 +64,19 @@ struct PPPlan {
   unsigned* flags;                  // [G][8]: wave w of workgroup g has published its part of slab g when flags[g][w] == epoch
 };
 
-template <int OFF> __device__ __forceinline__ void pp_read(pp_u32x4& d, unsigned addr) {
+// lds_read128_i (lds_asm.h) behind the ablation switch; the waits are lds_wait<0>
+template <int OFF> __device__ __forceinline__ void pp_read(u32x4& d, unsigned addr) {
   static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field is 16 bits");
 #if AS_PP_ABLATE & 2
   asm volatile("" : "=v"(d) : "v"(addr));
 #else
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
+  lds_read128_i<OFF>(d, addr);
 #endif
-}
-__device__ __forceinline__ void pp_wait12(pp_u32x4 (&x)[4][2], pp_u32x4 (&w)[2][2]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[1][0]), "+v"(x[1][1]), "+v"(x[2][0]), "+v"(x[2][1]), "+v"(x[3][0]),
-                 "+v"(x[3][1]), "+v"(w[0][0]), "+v"(w[0][1]), "+v"(w[1][0]), "+v"(w[1][1]));
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void pp_wait8(pp_u32x4 (&x)[4][2]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[1][0]), "+v"(x[1][1]), "+v"(x[2][0]), "+v"(x[2][1]), "+v"(x[3][0]),
-                 "+v"(x[3][1]));
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void pp_wait4(pp_u32x4 (&w)[2][2]) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(w[0][0]), "+v"(w[0][1]), "+v"(w[1][0]), "+v"(w[1][1]));
-  __builtin_amdgcn_sched_barrier(0);
 }
 
 // column of a 32-column block held by MFMA row j of the block's two 16-row fragments (j = 16 f + i, lane group g = i >> 2,
 // register r = i & 3): 8 g + 4 f + r -- fragment pair (f = 0, 1) gives lane group g the columns 8 g .. 8 g + 7
 __device__ __forceinline__ int pp_pi32(int j) { return 8 * ((j & 15) >> 2) + 4 * (j >> 4) + (j & 3); }
-
-template <int... I, typename F> __device__ __forceinline__ void pp_static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <typename F> __device__ __forceinline__ void g_static_for16(F&& f) {
-  pp_static_for_impl(std::make_integer_sequence<int, 16>{}, f);
-}
 
 template <int CFG> struct PPCfg;
 template <> struct PPCfg<0> {
@@ -289,7 +267,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const __bf16* __restric
   using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
 
   // ---- fragment read addresses (per lane): row i = lane & 15 of a 16-row fragment, chunk (lane >> 4) + 4 ks ----
-  const unsigned smem_base = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem;
+  const unsigned smem_base = lds_addr(smem);
   const unsigned frag_lane = (unsigned)(li * 128 + ((lg ^ ((li >> 1) & 7)) << 4));
   const unsigned ks1 = (frag_lane & 64u) ? (unsigned)-64 : 64u;   // k32 step 1 = chunk ^ 4 = +- 64 bytes (no alignment assumed)
   const unsigned x_lane = smem_base + frag_lane + (CFG == 0 ? wr * 64 * 128 : (wr & 1) * 64 * 128 + (wr >> 1) * C::X1);
@@ -306,13 +284,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const __bf16* __restric
   };
   zero_acc();
 
-  pp_u32x4 xf[4][2], wf[2][2];                               // [fragment][ks]
+  u32x4 xf[4][2], wf[2][2];                                  // [fragment][ks]
   // 16 MFMAs: m fragments A0 .. A0+3 x the two fragments of column block P, two k32 steps; D[n][m] = W . X^T
   auto mfma16 = [&](auto a0_c, auto p_c) {
     constexpr int A0 = decltype(a0_c)::value, P = decltype(p_c)::value;
     if (AS_PP_PRIO == 1) __builtin_amdgcn_s_setprio(1);
     if (AS_PP_PRIO == 2) __builtin_amdgcn_s_setprio(0);
-    g_static_for16([&](auto n_c) {
+    static_for<16>([&](auto n_c) {
       constexpr int n = decltype(n_c)::value, ks = n >> 3, a = (n >> 1) & 3, f = n & 1;
 #if AS_PP_ABLATE & 4
       auto& a_ = acc[A0 + a][P][f];
@@ -376,13 +354,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const __bf16* __restric
 #pragma unroll
     for (int a0 = 0; a0 < MA; a0 += 4) {
       // ACT 3: the pre-activations of these four row fragments, loaded (rows clamped: no branch) and waited for up front
-      pp_u32x4 pre[4][2];
+      u32x4 pre[4][2];
       if constexpr (EM == 0 && ACT == 3) {
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
           for (int p = 0; p < 2; ++p)
-            pre[a][p] = *reinterpret_cast<const pp_u32x4*>(reinterpret_cast<const __bf16*>(epi.q) +
+            pre[a][p] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(epi.q) +
                                                            (size_t)min(row0 + 16 * (a0 + a), M - 1) * Nout + colw + 32 * p);
 #pragma unroll
         for (int a = 0; a < 4; ++a) asm volatile("" : "+v"(pre[a][0]), "+v"(pre[a][1]));
@@ -425,7 +403,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const __bf16* __restric
               *reinterpret_cast<uint4*>(reinterpret_cast<__bf16*>(epi.q) + (size_t)row * Nout + col) = pk;
               *reinterpret_cast<uint4*>(out + (size_t)row * Nout + col) = gelu_chunk(pk);
             } else if constexpr (ACT == 3) {
-              const pp_u32x4 h = pre[a - a0][p];
+              const u32x4 h = pre[a - a0][p];
               *reinterpret_cast<uint4*>(out + (size_t)row * Nout + col) = dgelu_chunk(pk, make_uint4(h.x, h.y, h.z, h.w));
             } else {
               *reinterpret_cast<uint4*>(out + (size_t)row * Nout + col) = pk;
@@ -486,7 +464,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const __bf16* __restric
       for (int p = 0; p < 2; ++p)
 #pragma unroll
         for (int f = 0; f < 2; ++f)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pp_u32x4, acc[a][p][f]), rs_slab,
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[a][p][f]), rs_slab,
                                                  (int)(base + (unsigned)((a * 2 + p) * 2 + f) * 8192u), 0, 16 /* sc1: write-through */);
   };
   auto slab_publish = [&]() __attribute__((always_inline)) {                                // (every lane stores the same word: no divergent branch in the loop)
@@ -525,21 +503,22 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const __bf16* __restric
       read_w(std::integral_constant<int, C::W0>{}, wb);
       stage(I1{});
       bar();
-      pp_wait12(xf, wf);
+      lds_wait<0>(xf[0][0], xf[0][1], xf[1][0], xf[1][1], xf[2][0], xf[2][1], xf[3][0], xf[3][1],
+                  wf[0][0], wf[0][1], wf[1][0], wf[1][1]);
       mfma16(I0{}, I0{});
       bar_load();
       // phase 1: (M0, N1); W0 of step g + 1
       read_w(std::integral_constant<int, C::W1>{}, wb);
       stage(I2{});
       bar();
-      pp_wait4(wf);
+      lds_wait<0>(wf[0][0], wf[0][1], wf[1][0], wf[1][1]);
       mfma16(I0{}, I1{});
       bar_load();
       // phase 2: (M1, N1); X0 of step g + 2
       read_x(std::integral_constant<int, C::X1>{}, xb);
       stage(I0{});
       bar();
-      pp_wait8(xf);
+      lds_wait<0>(xf[0][0], xf[0][1], xf[1][0], xf[1][1], xf[2][0], xf[2][1], xf[3][0], xf[3][1]);
       mfma16(std::integral_constant<int, 4>{}, I1{});
       bar_load();
       // phase 3: (M1, N0); W1 of step g + 2.  Everything of step g + 1 has landed when at most the LDS-DMAs issued after its
@@ -548,7 +527,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const __bf16* __restric
       stage(I3{});
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       bar();
-      pp_wait4(wf);
+      lds_wait<0>(wf[0][0], wf[0][1], wf[1][0], wf[1][1]);
       mfma16(std::integral_constant<int, 4>{}, I0{});
       bar_load();
     } else {
@@ -557,7 +536,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const __bf16* __restric
       read_w(std::integral_constant<int, C::W0>{}, wb);
       stage(I1{});
       bar();
-      pp_wait12(xf, wf);
+      lds_wait<0>(xf[0][0], xf[0][1], xf[1][0], xf[1][1], xf[2][0], xf[2][1], xf[3][0], xf[3][1],
+                  wf[0][0], wf[0][1], wf[1][0], wf[1][1]);
       mfma16(I0{}, I0{});
       bar_load();
       // phase 1: (M, N1); W of step g + 2, X0 of step g + 3.  Step g + 1 has landed when at most the LDS-DMAs issued after ITS
@@ -567,7 +547,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const __bf16* __restric
       stage(I0{});
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       bar();
-      pp_wait4(wf);
+      lds_wait<0>(wf[0][0], wf[0][1], wf[1][0], wf[1][1]);
       mfma16(I0{}, I1{});
       bar_load();
     }

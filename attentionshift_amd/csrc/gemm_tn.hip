@@ -15,6 +15,7 @@
 // (autograd of models/vision_transformer.py:47-59, 75-77, 84; mae_bbox_head_rec.py:148-168).
 #include <utility>
 #include "common.h"
+#include "lds_asm.h"
 
 namespace {
 
@@ -27,26 +28,7 @@ constexpr int TN_NT = 256;
 constexpr int TN_TILE_B = TN_GM * TN_T * 2;        // 8 KiB: one operand tile of a stage
 constexpr int TN_STAGE_B = 2 * TN_TILE_B;          // dY tile | X tile
 
-typedef __attribute__((ext_vector_type(2))) unsigned tn_u32x2;
-
-__device__ __forceinline__ unsigned tn_lds_addr(const void* p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-__device__ __forceinline__ void tn_dma16(unsigned voff, const char* sbase, unsigned lds_dst) {
-  // global_load_lds_dwordx4, saddr form (see sdpa.hip lds_dma16): 64 lanes x 16 B from sbase + voff[lane] -> LDS [m0 + 16 lane]
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-template <int... I, typename F> __device__ __forceinline__ void static_for_tn_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F> __device__ __forceinline__ void static_for_tn(F&& f) {
-  static_for_tn_impl(std::make_integer_sequence<int, N>{}, f);
-}
-template <int OFF> __device__ __forceinline__ void tn_read_tr(tn_u32x2& dst, unsigned addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
+// LDS-DMA, hidden transposing reads and their wait, static_for: lds_asm.h
 
 // grid (tiles, S).  part: fp32 [S][Nout][K].  chunk: token rows per split (multiple of TN_GM).
 template <int TN_NSTAGE>
@@ -73,14 +55,14 @@ __global__ __launch_bounds__(TN_NT, TN_NSTAGE == 4 ? 2 : 3) void gemm_tn_splitk_
   const unsigned ld_col = (unsigned)(((lane & 15) ^ (ld_row << 2)) * 16);
   const char* const dy_b = reinterpret_cast<const char*>(dy) + (size_t)n0 * 2;
   const char* const x_b = reinterpret_cast<const char*>(x) + (size_t)k0 * 2;
-  const unsigned smem_base = tn_lds_addr(smem);
+  const unsigned smem_base = lds_addr(smem);
   auto stage = [&](int st, int buf) {
     const unsigned base = smem_base + buf * TN_STAGE_B;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int m = min(m_lo + st * TN_GM + (wave * 2 + j) * 4 + ld_row, M - 1);   // rows past the end re-read the last row (zeroed below)
-      tn_dma16((unsigned)m * (unsigned)(Nout * 2) + ld_col, dy_b, base + (wave * 2 + j) * 1024);
-      tn_dma16((unsigned)m * (unsigned)(K * 2) + ld_col, x_b, base + TN_TILE_B + (wave * 2 + j) * 1024);
+      lds_dma16((unsigned)m * (unsigned)(Nout * 2) + ld_col, dy_b, base + (wave * 2 + j) * 1024);
+      lds_dma16((unsigned)m * (unsigned)(K * 2) + ld_col, x_b, base + TN_TILE_B + (wave * 2 + j) * 1024);
     }
   };
 
@@ -116,7 +98,7 @@ __global__ __launch_bounds__(TN_NT, TN_NSTAGE == 4 ? 2 : 3) void gemm_tn_splitk_
   if (nst > 1) stage(1, 1);
   if (TN_NSTAGE == 4 && nst > 2) stage(2, 2);
   for (int st0 = 0; st0 < nst; st0 += TN_NSTAGE) {
-    static_for_tn<TN_NSTAGE>([&](auto slot_c) {
+    static_for<TN_NSTAGE>([&](auto slot_c) {
       constexpr int SLOT = decltype(slot_c)::value;
       const int st = st0 + SLOT;
       if (st >= nst) return;
@@ -130,28 +112,25 @@ __global__ __launch_bounds__(TN_NT, TN_NSTAGE == 4 ? 2 : 3) void gemm_tn_splitk_
       if (AS_TN_ABLATE != 1 && st + TN_NSTAGE - 1 < nst) stage(st + TN_NSTAGE - 1, (SLOT + TN_NSTAGE - 1) % TN_NSTAGE);
       // fragments of the stage: [operand][block][k16 step][read]; the first k16 step's eight reads are waited for alone
       // (LDS returns in order), so its MFMAs run while the second step's reads are still in flight
-      tn_u32x2 ra[2][2][2], rb[2][2][2];
+      u32x2 ra[2][2][2], rb[2][2][2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        tn_read_tr<SLOT * TN_STAGE_B + 0 * 4096 + 0 * 1024>(ra[i][0][0], fA[i]);
-        tn_read_tr<SLOT * TN_STAGE_B + 0 * 4096 + 1 * 1024>(ra[i][0][1], fA[i]);
-        tn_read_tr<SLOT * TN_STAGE_B + 0 * 4096 + 0 * 1024>(rb[i][0][0], fB[i]);
-        tn_read_tr<SLOT * TN_STAGE_B + 0 * 4096 + 1 * 1024>(rb[i][0][1], fB[i]);
+        lds_read_tr64_i<SLOT * TN_STAGE_B + 0 * 4096 + 0 * 1024>(ra[i][0][0], fA[i]);
+        lds_read_tr64_i<SLOT * TN_STAGE_B + 0 * 4096 + 1 * 1024>(ra[i][0][1], fA[i]);
+        lds_read_tr64_i<SLOT * TN_STAGE_B + 0 * 4096 + 0 * 1024>(rb[i][0][0], fB[i]);
+        lds_read_tr64_i<SLOT * TN_STAGE_B + 0 * 4096 + 1 * 1024>(rb[i][0][1], fB[i]);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        tn_read_tr<SLOT * TN_STAGE_B + 1 * 4096 + 0 * 1024>(ra[i][1][0], fA[i]);
-        tn_read_tr<SLOT * TN_STAGE_B + 1 * 4096 + 1 * 1024>(ra[i][1][1], fA[i]);
-        tn_read_tr<SLOT * TN_STAGE_B + 1 * 4096 + 0 * 1024>(rb[i][1][0], fB[i]);
-        tn_read_tr<SLOT * TN_STAGE_B + 1 * 4096 + 1 * 1024>(rb[i][1][1], fB[i]);
+        lds_read_tr64_i<SLOT * TN_STAGE_B + 1 * 4096 + 0 * 1024>(ra[i][1][0], fA[i]);
+        lds_read_tr64_i<SLOT * TN_STAGE_B + 1 * 4096 + 1 * 1024>(ra[i][1][1], fA[i]);
+        lds_read_tr64_i<SLOT * TN_STAGE_B + 1 * 4096 + 0 * 1024>(rb[i][1][0], fB[i]);
+        lds_read_tr64_i<SLOT * TN_STAGE_B + 1 * 4096 + 1 * 1024>(rb[i][1][1], fB[i]);
       }
       auto wait_step = [&](auto s_c, auto left_c) {
         constexpr int S_ = decltype(s_c)::value;
-        asm volatile("s_waitcnt lgkmcnt(%8)"
-                     : "+v"(ra[0][S_][0]), "+v"(ra[0][S_][1]), "+v"(ra[1][S_][0]), "+v"(ra[1][S_][1]), "+v"(rb[0][S_][0]),
-                       "+v"(rb[0][S_][1]), "+v"(rb[1][S_][0]), "+v"(rb[1][S_][1])
-                     : "n"(decltype(left_c)::value));
-        __builtin_amdgcn_sched_barrier(0);
+        lds_wait<decltype(left_c)::value>(ra[0][S_][0], ra[0][S_][1], ra[1][S_][0], ra[1][S_][1], rb[0][S_][0], rb[0][S_][1],
+                                          rb[1][S_][0], rb[1][S_][1]);
       };
       const int mrow = m_lo + st * TN_GM;                            // first token row of the stage
       const bool ragged = mrow + TN_GM > M;                          // only the last stage of the last split
@@ -226,15 +205,6 @@ __global__ __launch_bounds__(TN_NT, TN_NSTAGE == 4 ? 2 : 3) void gemm_tn_splitk_
 constexpr int TW_N = 256, TW_K = 128;
 constexpr int TW_A_B = TN_GM * TW_N * 2, TW_B_B = TN_GM * TW_K * 2, TW_STAGE_B = TW_A_B + TW_B_B;   // 16 + 8 KiB
 constexpr int TW_NSTAGE = 3;
-typedef short tw_i16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) const char* tw_lds_ptr;
-__device__ __forceinline__ void tw_frag(Frag<__bf16>& f, tw_lds_ptr p0, tw_lds_ptr p1) {
-  const tw_i16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tw_i16x4*)p0);
-  const tw_i16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tw_i16x4*)p1);
-  typedef short i16x8 __attribute__((ext_vector_type(8)));
-  const i16x8 w = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  f.v = __builtin_bit_cast(bf16x8, w);
-}
 
 __global__ __launch_bounds__(TN_NT, 2) void gemm_tn_wide_kernel(const __bf16* __restrict__ dy, const __bf16* __restrict__ x,
                                                               float* __restrict__ part, float* __restrict__ db_part, int M, int Nout,
@@ -257,30 +227,30 @@ __global__ __launch_bounds__(TN_NT, 2) void gemm_tn_wide_kernel(const __bf16* __
   const int a_row = lane >> 5, b_row = lane >> 4;                    // row inside a piece
   const char* const dy_b = reinterpret_cast<const char*>(dy) + (size_t)n0 * 2;
   const char* const x_b = reinterpret_cast<const char*>(x) + (size_t)k0 * 2;
-  const unsigned smem_base = tn_lds_addr(smem);
+  const unsigned smem_base = lds_addr(smem);
   auto stage = [&](int st, int buf) {
     const unsigned base = smem_base + buf * TW_STAGE_B;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int r = (wave * 4 + j) * 2 + a_row;                      // token row of the stage
       const int m = min(m_lo + st * TN_GM + r, M - 1);               // rows past the end re-read the last row (zeroed below)
-      tn_dma16((unsigned)m * (unsigned)(Nout * 2) + (unsigned)(((lane & 31) ^ ((r & 3) << 2)) * 16), dy_b, base + (wave * 4 + j) * 1024);
+      lds_dma16((unsigned)m * (unsigned)(Nout * 2) + (unsigned)(((lane & 31) ^ ((r & 3) << 2)) * 16), dy_b, base + (wave * 4 + j) * 1024);
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int r = (wave * 2 + j) * 4 + b_row;
       const int m = min(m_lo + st * TN_GM + r, M - 1);
-      tn_dma16((unsigned)m * (unsigned)(K * 2) + (unsigned)(((lane & 15) ^ ((r & 3) << 2)) * 16), x_b, base + TW_A_B + (wave * 2 + j) * 1024);
+      lds_dma16((unsigned)m * (unsigned)(K * 2) + (unsigned)(((lane & 15) ^ ((r & 3) << 2)) * 16), x_b, base + TW_A_B + (wave * 2 + j) * 1024);
     }
   };
 
   // ---- fragment pointers (slot 0, k16 step 0, read 0): the 16-lane group g = lane >> 4 reads rows 8 (g >> 1) + (t >> 2) [+ 16 s
   // + 4 q as immediates], columns 32 blk + 16 (g & 1) + 4 (t & 3) .. +3 of the block; chunk = 4 blk' + 2 (g & 1) + ((t & 3) >> 1)
-  tw_lds_ptr pa[4], pb[2];
+  lds_ptr pa[4], pb[2];
   {
     const int g = lane >> 4, t = lane & 15;
     const int rowl = 8 * (g >> 1) + (t >> 2), lowc = 2 * (g & 1) + ((t & 3) >> 1), sw = (t >> 2) << 2, sub = (t & 1) * 8;
-    const tw_lds_ptr base = (tw_lds_ptr)smem;
+    const lds_ptr base = (lds_ptr)smem;
 #pragma unroll
     for (int i = 0; i < 4; ++i) pa[i] = base + (rowl * 512 + ((((wm * 4 + i) * 4 + lowc) ^ sw) << 4) + sub);
 #pragma unroll
@@ -300,7 +270,7 @@ __global__ __launch_bounds__(TN_NT, 2) void gemm_tn_wide_kernel(const __bf16* __
   stage(0, 0);
   if (nst > 1) stage(1, 1);
   for (int st0 = 0; st0 < nst; st0 += TW_NSTAGE) {
-    static_for_tn<TW_NSTAGE>([&](auto slot_c) {
+    static_for<TW_NSTAGE>([&](auto slot_c) {
       constexpr int SLOT = decltype(slot_c)::value;
       const int st = st0 + SLOT;
       if (st >= nst) return;
@@ -318,9 +288,9 @@ __global__ __launch_bounds__(TN_NT, 2) void gemm_tn_wide_kernel(const __bf16* __
       for (int sk = 0; sk < 2; ++sk) {
         constexpr int O = SLOT * TW_STAGE_B;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) tw_frag(fa[sk][i], pa[i] + (O + (16 * sk) * 512), pa[i] + (O + (16 * sk + 4) * 512));
+        for (int i = 0; i < 4; ++i) lds_frag_tr(fa[sk][i], pa[i] + (O + (16 * sk) * 512), pa[i] + (O + (16 * sk + 4) * 512));
 #pragma unroll
-        for (int j = 0; j < 2; ++j) tw_frag(fb[sk][j], pb[j] + (O + (16 * sk) * 256), pb[j] + (O + (16 * sk + 4) * 256));
+        for (int j = 0; j < 2; ++j) lds_frag_tr(fb[sk][j], pb[j] + (O + (16 * sk) * 256), pb[j] + (O + (16 * sk + 4) * 256));
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll

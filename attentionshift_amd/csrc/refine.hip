@@ -864,16 +864,6 @@ __global__ __launch_bounds__(RF_NT) void mask_count_kernel(const uint8_t* __rest
   if (tid == 0 && sh[0] != 0) atomicAdd(&counts[m], sh[0]);
 }
 
-__device__ __forceinline__ int wave_excl_scan(int v, int lane) {
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(inc, o);
-    if (lane >= o) inc += u;
-  }
-  return inc - v;
-}
-
 // result of one (row, rank): the flat index, and / or its (x, y) [or (y, x)] coordinates on a W-wide grid as int64 with an
 // out-of-range rank (-1) clamped to pixel 0 -- what the callers' `clamp(min=0)`, `% W`, `// W`, `stack` chain produced
 // (as_rank_draw_xy only) patch: the index of the selected pixel's patch on a patch_w-wide grid of patch_div-pixel patches,
@@ -920,7 +910,7 @@ __global__ __launch_bounds__(64) void rank_select_kernel(const uint8_t* __restri
   } else {
     for (int i = lane * cpl; i < min((lane + 1) * cpl, nchunk); ++i) mine += c[i];
   }
-  const int before = wave_excl_scan(mine, lane);
+  const int before = wave_incl_scan(mine, lane) - mine;
   if (MODE != 0) {
     const int n = __shfl(before + mine, 63);       // the row's population
     if (MODE == 1) r = min((int)(uk * (float)n), max(n - 1, 0));
@@ -973,7 +963,7 @@ __global__ __launch_bounds__(64) void rank_select_kernel(const uint8_t* __restri
       if (chunk * RS_CHUNK + off + i < HW && mask[base + off + i] != 0) occ |= 1ull << i;
   }
   const int cnt = __popcll(occ);
-  const int b2 = wave_excl_scan(cnt, lane);
+  const int b2 = wave_incl_scan(cnt, lane) - cnt;
   const unsigned long long hit2 = __ballot(rem >= b2 && rem < b2 + cnt);
   const int owner2 = __ffsll((long long)hit2) - 1;
   if (lane == owner2) {

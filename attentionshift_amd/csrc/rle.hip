@@ -117,12 +117,7 @@ __global__ __launch_bounds__(RLE_NT) void rle_count_kernel(const uint8_t* __rest
 // exclusive scan over the RLE_NT threads of a workgroup; sm holds RLE_WAVES values
 template <typename T> __device__ __forceinline__ T block_excl_scan(T v, T& total, T* sm) {
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  T inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
+  const T inc = wave_incl_scan(v, lane);
   __syncthreads();                                     // the previous call's reads of sm are done
   if (lane == 63) sm[wv] = inc;
   __syncthreads();

@@ -12,6 +12,7 @@
 // as its B operand without any data movement (same trick as sdpa.hip).
 #include <stdlib.h>
 #include "common.h"
+#include "lds_asm.h"
 
 namespace {
 
@@ -465,42 +466,7 @@ constexpr int R4_STAGE = R4_LSE + 1024;                    // + lse rows [head][
 #endif
 template <int NIB> struct R4Cfg { static constexpr int NSTAGE = NIB == 1 ? 2 : 3, OCC = NIB == 1 ? AS_R4_OCC1 : 2; };
 
-typedef __attribute__((ext_vector_type(4))) unsigned r4_u32x4;
-template <int OFF> __device__ __forceinline__ void r4_lds_read128(r4_u32x4& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-__device__ __forceinline__ void r4_lds_read128_dyn(r4_u32x4& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr));
-}
-__device__ __forceinline__ void r4_wait_lds(r4_u32x4& a, r4_u32x4& b, r4_u32x4& c, r4_u32x4& d) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void r4_wait_lds8(r4_u32x4& a, r4_u32x4& b, r4_u32x4& c, r4_u32x4& d, r4_u32x4& e, r4_u32x4& f,
-                                             r4_u32x4& g, r4_u32x4& h) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void r4_lds_read32(float& dst, unsigned addr) {
-  asm volatile("ds_read_b32 %0, %1" : "=v"(dst) : "v"(addr));
-}
-__device__ __forceinline__ void r4_wait_lds2(r4_u32x4& a, r4_u32x4& b) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b));
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// global_load_lds, saddr form: 64 lanes x 16 (4) B from sbase + voff[lane] -> LDS [dst + 16 (4) * lane]; m0 is saved and
-// restored in the same statement; `sbase` and `dst` are wave-uniform (as sdpa.hip's lds_dma16)
-__device__ __forceinline__ void r4_dma16(unsigned voff, const char* sbase, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(dst) : "memory");
-}
-__device__ __forceinline__ void r4_dma4(unsigned voff, const char* sbase, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(dst) : "memory");
-}
+// LDS-DMA (lds_dma16 / lds_dma4), hidden fragment reads and their waits: lds_asm.h
 
 template <int NIB>                                       // 32-row blocks of R carried (1: Trows <= 32, else 4)
 __global__ __launch_bounds__(RO_NT, R4Cfg<NIB>::OCC) void rollout_step4_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
@@ -533,7 +499,7 @@ __global__ __launch_bounds__(RO_NT, R4Cfg<NIB>::OCC) void rollout_step4_kernel(c
   // (7 LDS-DMA instructions).  Q and R are fragment-major: a piece is 1 KiB contiguous, lane l takes bytes 16 l, so the
   // address is a wave-uniform base (scalar registers, advanced per block) + one loop-invariant lane offset.
   const int ibw = min(wave, nib - 1);
-  const unsigned smem_u = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem;
+  const unsigned smem_u = lds_addr(smem);
   const unsigned voff = lane * 16;
   const char* q_w = reinterpret_cast<const char*>(q) + ((bh0 + wave) * (size_t)(Npad >> 5)) * 4096;   // [row block][k16 step][1 KiB]
   const char* r_w = reinterpret_cast<const char*>(rf_in) + rf_frag(b, nkb, 0, ibw, 0, 0) * sizeof(__bf16);
@@ -542,14 +508,14 @@ __global__ __launch_bounds__(RO_NT, R4Cfg<NIB>::OCC) void rollout_step4_kernel(c
     const unsigned base = smem_u + buf * R4_STAGE;
     const char* qs = q_w + (size_t)kb * 4096;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) r4_dma16(voff, qs + ks * 1024, base + (wave * 4 + ks) * 1024);
+    for (int ks = 0; ks < 4; ++ks) lds_dma16(voff, qs + ks * 1024, base + (wave * 4 + ks) * 1024);
     if (NIB == 4 || wave == 0) {                         // NIB == 1: only R block 0 exists, wave 0 brings it
       const char* rs = r_w + (size_t)kb * (4 * 2 * 1024);
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) r4_dma16(voff, rs + s2 * 1024, base + R4_QBYTES + (wave * 2 + s2) * 1024);
+      for (int s2 = 0; s2 < 2; ++s2) lds_dma16(voff, rs + s2 * 1024, base + R4_QBYTES + (wave * 2 + s2) * 1024);
     }
     // lse of head `wave`, rows of the block (an ordinary load here would make hipcc drain vmcnt(0) every iteration)
-    r4_dma4((unsigned)min(kb * 32 + li, N - 1) * 4u, l_w, base + R4_LSE + wave * 256);
+    lds_dma4((unsigned)min(kb * 32 + li, N - 1) * 4u, l_w, base + R4_LSE + wave * 256);
   };
 
   f32x16 acc[NIB];
@@ -558,7 +524,7 @@ __global__ __launch_bounds__(RO_NT, R4Cfg<NIB>::OCC) void rollout_step4_kernel(c
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[ib][r] = 0.0f;
   const float inv_h = 1.0f / (float)h;
-  const unsigned lbase = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem + lane * 16;
+  const unsigned lbase = lds_addr(smem) + lane * 16;
 
   if (nblk > 0) stage(kb0, 0);
   if (R4_NSTAGE > 2 && nblk > 1) stage(kb0 + 1, 1);
@@ -575,7 +541,7 @@ __global__ __launch_bounds__(RO_NT, R4Cfg<NIB>::OCC) void rollout_step4_kernel(c
       // the lse rows this wave brought (head `wave`, lane l = row l % 32) become -log2(e) * lse IN PLACE: the scores'
       // accumulators start from them (below), so the term costs no MFMA and no per-score VALU
       float own;
-      const unsigned a_own = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem + buf * R4_STAGE + R4_LSE + wave * 256 + lane * 4;
+      const unsigned a_own = lds_addr(smem) + buf * R4_STAGE + R4_LSE + wave * 256 + lane * 4;
       asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(own) : "v"(a_own) : "memory");
       own *= -LOG2E;
       asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(a_own), "v"(own) : "memory");
@@ -585,38 +551,36 @@ __global__ __launch_bounds__(RO_NT, R4Cfg<NIB>::OCC) void rollout_step4_kernel(c
     const unsigned sb = lbase + buf * R4_STAGE;
     // -log2(e) * lse of the block's 32 rows in ACCUMULATOR layout: register r of a lane in half `half` is row
     // (r & 3) + 8 (r >> 2) + 4 half, i.e. four runs of 4 consecutive rows = four 16-byte (broadcast) reads per head
-    const unsigned cb = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem + buf * R4_STAGE + R4_LSE + half * 16;
-    r4_u32x4 fc[2][4];
-    auto read_c = [&](int hh, r4_u32x4 (&c)[4]) {
+    const unsigned cb = lds_addr(smem) + buf * R4_STAGE + R4_LSE + half * 16;
+    u32x4 fc[2][4];
+    auto read_c = [&](int hh, u32x4 (&c)[4]) {
       const unsigned a = cb + hh * 256;
-      r4_lds_read128_dyn(c[0], a);
-      r4_lds_read128<32>(c[1], a);
-      r4_lds_read128<64>(c[2], a);
-      r4_lds_read128<96>(c[3], a);
+      lds_read128(c[0], a);
+      lds_read128_i<32>(c[1], a);
+      lds_read128_i<64>(c[2], a);
+      lds_read128_i<96>(c[3], a);
     };
     f32x16 pbar;
 #pragma unroll
     for (int r = 0; r < 16; ++r) pbar[r] = 0.0f;
     // software pipeline over the heads: the q.k MFMAs of head hh+1 are issued before the exp2 pass of head hh, the R
     // fragments are fetched under the last head's exp2 pass, and the eight R . Pbar MFMAs run as four independent chains
-    r4_u32x4 fa[2][4];
+    u32x4 fa[2][4];
     read_c(0, fc[0]);
-    r4_lds_read128_dyn(fa[0][0], sb);
-    r4_lds_read128<1024>(fa[0][1], sb);
-    r4_lds_read128<2048>(fa[0][2], sb);
-    r4_lds_read128<3072>(fa[0][3], sb);
+    lds_read128(fa[0][0], sb);
+    lds_read128_i<1024>(fa[0][1], sb);
+    lds_read128_i<2048>(fa[0][2], sb);
+    lds_read128_i<3072>(fa[0][3], sb);
     {
       const unsigned a1 = sb + 4096;
       read_c(1, fc[1]);
-      r4_lds_read128_dyn(fa[1][0], a1);
-      r4_lds_read128<1024>(fa[1][1], a1);
-      r4_lds_read128<2048>(fa[1][2], a1);
-      r4_lds_read128<3072>(fa[1][3], a1);
+      lds_read128(fa[1][0], a1);
+      lds_read128_i<1024>(fa[1][1], a1);
+      lds_read128_i<2048>(fa[1][2], a1);
+      lds_read128_i<3072>(fa[1][3], a1);
     }
-    asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[0][2]), "+v"(fa[0][3]), "+v"(fc[0][0]),
-                 "+v"(fc[0][1]), "+v"(fc[0][2]), "+v"(fc[0][3]));
-    __builtin_amdgcn_sched_barrier(0);
-    auto qk = [&](int hh, r4_u32x4 (&f)[4], r4_u32x4 (&c)[4]) {
+    lds_wait<8>(fa[0][0], fa[0][1], fa[0][2], fa[0][3], fc[0][0], fc[0][1], fc[0][2], fc[0][3]);
+    auto qk = [&](int hh, u32x4 (&f)[4], u32x4 (&c)[4]) {
       f32x16 sc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) sc[r] = __uint_as_float(c[r >> 2][r & 3]);
@@ -630,28 +594,28 @@ __global__ __launch_bounds__(RO_NT, R4Cfg<NIB>::OCC) void rollout_step4_kernel(c
       return sc;
     };
     f32x16 sc_cur = qk(0, fa[0], fc[0]);
-    r4_u32x4 fr[NIB][2];
+    u32x4 fr[NIB][2];
 #pragma unroll
     for (int hh = 0; hh < R4_HPG; ++hh) {
       f32x16 sc_next;
       if (hh + 1 < R4_HPG) {
         const int nx = (hh + 1) & 1;
-        r4_wait_lds8(fa[nx][0], fa[nx][1], fa[nx][2], fa[nx][3], fc[nx][0], fc[nx][1], fc[nx][2], fc[nx][3]);
+        lds_wait<0>(fa[nx][0], fa[nx][1], fa[nx][2], fa[nx][3], fc[nx][0], fc[nx][1], fc[nx][2], fc[nx][3]);
         sc_next = qk(hh + 1, fa[nx], fc[nx]);
         if (hh + 2 < R4_HPG) {                           // head hh+2's fragments into the buffer head hh just released
           const unsigned a2 = sb + (hh + 2) * 4096;
           read_c(hh + 2, fc[hh & 1]);
-          r4_lds_read128_dyn(fa[hh & 1][0], a2);
-          r4_lds_read128<1024>(fa[hh & 1][1], a2);
-          r4_lds_read128<2048>(fa[hh & 1][2], a2);
-          r4_lds_read128<3072>(fa[hh & 1][3], a2);
+          lds_read128(fa[hh & 1][0], a2);
+          lds_read128_i<1024>(fa[hh & 1][1], a2);
+          lds_read128_i<2048>(fa[hh & 1][2], a2);
+          lds_read128_i<3072>(fa[hh & 1][3], a2);
         }
       } else {
 #pragma unroll
         for (int ib = 0; ib < NIB; ++ib) {
           const unsigned a = sb + R4_QBYTES + min(ib, nib - 1) * 2048;
-          r4_lds_read128_dyn(fr[ib][0], a);
-          r4_lds_read128<1024>(fr[ib][1], a);
+          lds_read128(fr[ib][0], a);
+          lds_read128_i<1024>(fr[ib][1], a);
         }
       }
 #pragma unroll
@@ -666,13 +630,8 @@ __global__ __launch_bounds__(RO_NT, R4Cfg<NIB>::OCC) void rollout_step4_kernel(c
 #pragma unroll
       for (int r = 0; r < 16; ++r) fp[r >> 3].set(r & 7, kb * 32 + acc_row(r, half) < N ? pbar[r] : 0.0f);
     }
-    if constexpr (NIB == 1) {
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fr[0][0]), "+v"(fr[0][1]));
-    } else {
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fr[0][0]), "+v"(fr[0][1]), "+v"(fr[1][0]), "+v"(fr[1][1]), "+v"(fr[2][0]),
-                   "+v"(fr[2][1]), "+v"(fr[3][0]), "+v"(fr[3][1]));
-    }
-    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (NIB == 1) lds_wait<0>(fr[0][0], fr[0][1]);
+    else lds_wait<0>(fr[0][0], fr[0][1], fr[1][0], fr[1][1], fr[2][0], fr[2][1], fr[3][0], fr[3][1]);
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll

@@ -47,9 +47,6 @@ struct RpnNorm {
   float mean[4], std[4];
 };
 
-__device__ __forceinline__ float nan_max(float a, float b) { return (a != a || a > b) ? a : b; }
-__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || a < b) ? a : b; }
-
 // ascending in this = descending in the logit
 __device__ __forceinline__ unsigned desc_key(float v) {
   if (v != v) return 0u;
@@ -87,33 +84,6 @@ __device__ __forceinline__ void scan_planes(const float* __restrict__ cls, int A
         const int p = base + u * RPN_NT + tid;
         if (p < HW) f(desc_key(v[u]), p * A + a);
       }
-    }
-  }
-}
-
-__device__ __forceinline__ unsigned wave_incl_scan(unsigned v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// ascending bitonic sort of a[0..P) in LDS, P a power of two >= 2; ends with a barrier
-__device__ __forceinline__ void bitonic_sort(unsigned long long* a, int P, int tid) {
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < (P >> 1); t += RPN_NT) {
-        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-        const unsigned long long x = a[lo], y = a[hi];
-        const bool asc = (lo & size) == 0;
-        if ((x > y) == asc) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-      __syncthreads();
     }
   }
 }
@@ -183,7 +153,7 @@ __global__ __launch_bounds__(RPN_NT) void rpn_select_kernel(RpnLevels lv, int L,
       while (P2 < (int)nt) P2 <<= 1;
       for (int j = (int)nt + tid; j < P2; j += RPN_NT) cand[j] = ~0ull;
       __syncthreads();
-      bitonic_sort(cand, P2, tid);
+      bitonic_sort<unsigned long long, RPN_NT>(cand, P2, tid);
       for (unsigned j = tid; j < krem; j += RPN_NT) buf[nbelow + j] = cand[j];
     } else {
       // many keys share the first digit (ties, or a very narrow distribution): two more digits give T = the k-th smallest
@@ -247,7 +217,7 @@ __global__ __launch_bounds__(RPN_NT) void rpn_select_kernel(RpnLevels lv, int L,
     }
   }
   __syncthreads();
-  bitonic_sort(buf, P, tid);                               // the padding (~0) stays behind the k keys
+  bitonic_sort<unsigned long long, RPN_NT>(buf, P, tid);    // the padding (~0) stays behind the k keys
   unsigned long long* out = keys + (size_t)b * C + lv.off[l];
   for (int j = tid; j < k; j += RPN_NT) out[j] = buf[j];
 }

@@ -197,15 +197,6 @@ __global__ __launch_bounds__(RT_NT) void rpn_rule_kernel(RtLevels lv, int L, int
   }
 }
 
-__device__ __forceinline__ int wave_incl_scan_i(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-
 // one workgroup per image: blk_cnt -> its exclusive scan (in place), counts [B,2] <- the totals
 __global__ __launch_bounds__(RT_SNT) void rpn_scan_kernel(int nblk, int* __restrict__ blk_cnt, int* __restrict__ counts) {
   __shared__ int wsum[2][2][RT_SWAVES];
@@ -215,7 +206,7 @@ __global__ __launch_bounds__(RT_SNT) void rpn_scan_kernel(int nblk, int* __restr
   for (int base = 0; base < nblk; base += RT_SNT) {
     const int j = base + tid;
     const int v0 = j < nblk ? c[2 * j] : 0, v1 = j < nblk ? c[2 * j + 1] : 0;
-    const int i0 = wave_incl_scan_i(v0, lane), i1 = wave_incl_scan_i(v1, lane);
+    const int i0 = wave_incl_scan(v0, lane), i1 = wave_incl_scan(v1, lane);
     if (lane == 63) {
       wsum[parity][0][wave] = i0;
       wsum[parity][1][wave] = i1;
@@ -242,24 +233,6 @@ __global__ __launch_bounds__(RT_SNT) void rpn_scan_kernel(int nblk, int* __restr
   if (tid == 0) {
     counts[2 * b] = carry0;
     counts[2 * b + 1] = carry1;
-  }
-}
-
-// ascending bitonic sort of a[0..P) in LDS, P a power of two >= 2; ends with a barrier
-__device__ __forceinline__ void bitonic_sort_i(int* a, int P, int tid) {
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < (P >> 1); t += RT_SNT) {
-        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-        const int x = a[lo], y = a[hi];
-        const bool asc = (lo & size) == 0;
-        if ((x > y) == asc) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
   }
 }
 
@@ -302,7 +275,7 @@ __global__ __launch_bounds__(RT_SNT) void rpn_sample_kernel(int T, int nblk, int
     }
   }
   __syncthreads();
-  bitonic_sort_i(buf, P, tid);
+  bitonic_sort<int, RT_SNT>(buf, P, tid);
   int* o = out + ((size_t)b * 2 + set) * num;
   for (int j = tid; j < num; j += RT_SNT) {
     const int v = j < n ? buf[j] : INT_MAX;

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <utility>
 #include "common.h"
+#include "lds_asm.h"
 
 namespace {
 
@@ -228,43 +229,7 @@ __global__ __launch_bounds__(SD_NT) void sdpa_fwd_kernel(const T* __restrict__ q
 // c ^ ((r >> 1) & 7).  Rows are 128 B, so rows 2j and 2j+1 fill one 256-B bank row and share a key; the 16-lane
 // groups ds_read_b128 is serviced in ({0-3,12-15,20-27}, ...; MI355X_MICROARCH.md, LDS) then hit 16 distinct slots.  Padded keys of the last tile are zeroed in LDS (P is exactly 0 there, but 0 * garbage must stay 0).
 // ---------------------------------------------------------------------------------------------------------
-// LDS reads the compiler must NOT see: after an LDS-DMA hipcc drains vmcnt(0) before any ds_read it can see (it cannot
-// prove the read does not alias the DMA destination), which would collapse the 3-deep ring to depth 0.  The reads are
-// issued in inline asm and completed by lds_wait<>, which names every destination as read-write so nothing is
-// consumed early (cdna_hip_programming.md section 5.7, form ii), followed by a sched_barrier (rule 18).
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-__device__ __forceinline__ void lds_read128(u32x4& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr));
-}
-__device__ __forceinline__ void lds_read64(u32x2& dst, unsigned addr) {
-  asm volatile("ds_read_b64 %0, %1" : "=v"(dst) : "v"(addr));
-}
-// immediate-offset forms: the per-lane address register is loop-invariant, ring slot / row block are immediates
-template <int OFF> __device__ __forceinline__ void lds_read128_i(u32x4& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-template <int OFF> __device__ __forceinline__ void lds_read64_i(u32x2& dst, unsigned addr) {
-  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-template <int... I, typename F> __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
-__device__ __forceinline__ void lds_wait4(u32x4& a, u32x4& b, u32x4& c, u32x4& d) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void lds_wait8(u32x2 (&v)[8]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
-  __builtin_amdgcn_sched_barrier(0);
-}
+// The fragment reads are hidden from the compiler and completed by lds_wait<> (lds_asm.h, top comment).
 
 #ifndef AS_SDPA_NBUF2
 #define AS_SDPA_NBUF2 3           // LDS ring depth of sdpa_fwd_pipe_kernel<2, ...> (3 or 4 slots of 16 KiB)
@@ -420,7 +385,7 @@ __global__ __launch_bounds__(SD_NT, 3) void sdpa_fwd_glds_kernel(const __bf16* _
       u32x4 kf[4];
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) lds_read128_i<OFF>(kf[ks], koff[ks]);
-      lds_wait4(kf[0], kf[1], kf[2], kf[3]);
+      lds_wait<0>(kf[0], kf[1], kf[2], kf[3]);
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         Frag<__bf16> fk;
@@ -500,7 +465,7 @@ __global__ __launch_bounds__(SD_NT, 3) void sdpa_fwd_glds_kernel(const __bf16* _
       u32x4 vf[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) lds_read128_i<OFF>(vf[c], voff[c]);
-      lds_wait4(vf[0], vf[1], vf[2], vf[3]);
+      lds_wait<0>(vf[0], vf[1], vf[2], vf[3]);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         Frag<__bf16> fv;
@@ -562,19 +527,12 @@ __global__ __launch_bounds__(SD_NT, 3) void sdpa_fwd_glds_kernel(const __bf16* _
 // NQ = 2: a wave owns 64 queries (two query blocks), a tile is four units ordered (key half, query block) so each K / V^T
 // fragment read feeds two MFMAs; 2 workgroups per CU.
 //
-// The LDS-DMA is issued from inline asm, so hipcc sees no vm-counted LDS write and treats the fragment reads as ordinary
+// The LDS-DMA is issued from inline asm (lds_dma16, lds_asm.h), so hipcc sees no vm-counted LDS write and treats the fragment reads as ordinary
 // LDS loads: it places them, counts their lgkmcnt and interleaves them itself (the other kernel has to hide every
 // ds_read in asm).  Ring protocol, ONE barrier per tile: in the middle of the first step of tile kt (after the last LDS
 // read of tile kt-1, before the first of tile kt+1) every wave drains its reads, waits for its own pieces of tile kt+1
 // (the only DMA outstanding), passes the barrier and issues tile kt+2 into the slot of tile kt-1.
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void lds_dma16(unsigned voff, const char* sbase, unsigned lds_dst) {
-  // global_load_lds_dwordx4, saddr form: 64 lanes x 16 B from sbase + voff[lane] -> LDS [m0 + lane * 16]; m0 is saved
-  // and restored in the same statement (cdna_hip_programming.md 5.7).  `sbase` and `lds_dst` must be wave-uniform.
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
 
 // MODE 0: softmax referenced to the row max of a query block's first unit, re-referenced when a unit sum leaves 1e20
 //         (exactly sdpa_fwd_glds_kernel's arithmetic).

@@ -28,11 +28,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lds_asm.h"
 
 namespace {
 
 constexpr int BW_NT = 256, BW_HD = 64, BW_TILE = 64;
-typedef __attribute__((ext_vector_type(4))) unsigned bw_u32x4;   // plain vector type: staging arrays stay in VGPRs
 
 __device__ __forceinline__ int pi_row(int i) { return (i & 0x13) | ((i & 4) << 1) | ((i & 8) >> 1); }
 // accumulator register r of a lane in half `half` <-> row inside a 32-row block when the rows were fed through pi
@@ -80,21 +80,21 @@ template <typename T> struct TileStage {
   static constexpr int CH = BW_TILE * CPR / BW_NT;          // chunks per thread
 };
 template <typename T>
-__device__ __forceinline__ void tile_load(bw_u32x4 (&r)[TileStage<T>::CH], const char* src, size_t src_row_stride, int tid) {
+__device__ __forceinline__ void tile_load(u32x4 (&r)[TileStage<T>::CH], const char* src, size_t src_row_stride, int tid) {
   constexpr int CPR = TileStage<T>::CPR;
 #pragma unroll
   for (int i = 0; i < TileStage<T>::CH; ++i) {
     const int c = tid + i * BW_NT;
-    r[i] = *reinterpret_cast<const bw_u32x4*>(src + (size_t)(c / CPR) * src_row_stride + (c % CPR) * 16);
+    r[i] = *reinterpret_cast<const u32x4*>(src + (size_t)(c / CPR) * src_row_stride + (c % CPR) * 16);
   }
 }
 template <typename T>
-__device__ __forceinline__ void tile_store(const bw_u32x4 (&r)[TileStage<T>::CH], char* dst, int pitch, int tid) {
+__device__ __forceinline__ void tile_store(const u32x4 (&r)[TileStage<T>::CH], char* dst, int pitch, int tid) {
   constexpr int CPR = TileStage<T>::CPR;
 #pragma unroll
   for (int i = 0; i < TileStage<T>::CH; ++i) {
     const int c = tid + i * BW_NT;
-    *reinterpret_cast<bw_u32x4*>(dst + (c / CPR) * pitch + (c % CPR) * 16) = r[i];
+    *reinterpret_cast<u32x4*>(dst + (c / CPR) * pitch + (c % CPR) * 16) = r[i];
   }
 }
 
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(BW_NT, sizeof(T) == 2 ? 2 : 1) void sdpa_bwd_dq_ker
   const char* ksrc = reinterpret_cast<const char*>(k + (size_t)bh * Npad * BW_HD);
   const char* vsrc = reinterpret_cast<const char*>(vrow + (size_t)bh * Npad * BW_HD);
   const char* ktsrc = reinterpret_cast<const char*>(kt + (size_t)bh * BW_HD * Npad);
-  bw_u32x4 sk[TS::CH], sv[TS::CH], skt[TS::CH];
+  u32x4 sk[TS::CH], sv[TS::CH], skt[TS::CH];
 #define GLOAD(t)                                                                         \
   do {                                                                                   \
     tile_load<T>(sk, ksrc + (size_t)(t) * BW_TILE * TS::ROWB, TS::ROWB, tid);            \
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(BW_NT, sizeof(T) == 2 ? 2 : 1) void sdpa_bwd_dkv_ke
   const char* dosrc = reinterpret_cast<const char*>(dof + (size_t)bh * Npad * BW_HD);
   const char* qtsrc = reinterpret_cast<const char*>(qt + (size_t)bh * BW_HD * Npad);
   const char* dotsrc = reinterpret_cast<const char*>(dot + (size_t)bh * BW_HD * Npad);
-  bw_u32x4 sq[TS::CH], sdo[TS::CH], sqt[TS::CH], sdot[TS::CH];
+  u32x4 sq[TS::CH], sdo[TS::CH], sqt[TS::CH], sdot[TS::CH];
   float stat = 0.0f;                                 // threads 0..63: lse*log2e, 64..127: delta
 #define GLOAD(t)                                                                                                   \
   do {                                                                                                             \
@@ -609,17 +609,7 @@ __global__ __launch_bounds__(BW_NT, sizeof(T) == 2 ? 2 : 1) void sdpa_bwd_dkv_ke
 #endif
 constexpr int DK_QF = 0, DK_DOF = 8192, DK_QT = 16384, DK_DOT = 24576, DK_ST = 32768, DK_STAGE = 33280;
 
-__device__ __forceinline__ void bw_dma16(unsigned voff, const char* sbase, unsigned dst) {
-  unsigned keep;   // global_load_lds_dwordx4, saddr form: 64 lanes x 16 B from sbase + voff[lane] -> LDS [dst + 16 * lane]
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(dst) : "memory");
-}
-__device__ __forceinline__ void bw_dma4(unsigned voff, const char* sbase, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(dst) : "memory");
-}
-__device__ __forceinline__ int bw_swz(int r) { return ((r >> 1) & 3) | (((r >> 4) & 1) << 2); }   // gemm.hip g_swz<4>
+// LDS-DMA (lds_dma16 / lds_dma4) and the chunk swizzle of the 128-byte tile rows (lds_swz_row<4>): lds_asm.h
 
 // NK blocks of 32 keys per wave (every fragment read of the query tile feeds NK MFMAs), NW waves per workgroup (each staged
 // query tile serves 32 * NK * NW keys) -- see sdpa_bwd_dq_dma_kernel for the LDS-pipe arithmetic behind both.  A key's sums
@@ -656,7 +646,7 @@ __global__ __launch_bounds__(64 * NW, 2) void sdpa_bwd_dkv_dma_kernel(const __bf
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(fk[nk][0].v), "+v"(fk[nk][1].v), "+v"(fk[nk][2].v), "+v"(fk[nk][3].v), "+v"(fv[nk][0].v),
                  "+v"(fv[nk][1].v), "+v"(fv[nk][2].v), "+v"(fv[nk][3].v));
 
-  const unsigned smem_u = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem;
+  const unsigned smem_u = lds_addr(smem);
   const char* qf_b = reinterpret_cast<const char*>(q + (size_t)bh * Npad * BW_HD);
   const char* dof_b = reinterpret_cast<const char*>(dof + (size_t)bh * Npad * BW_HD);
   const char* qt_b = reinterpret_cast<const char*>(qt + (size_t)bh * BW_HD * Npad);
@@ -668,20 +658,20 @@ __global__ __launch_bounds__(64 * NW, 2) void sdpa_bwd_dkv_dma_kernel(const __bf
 #pragma unroll
   for (int j = 0; j < PPW; ++j) {
     const int r = (wave * PPW + j) * 8 + (lane >> 3);
-    voff_t[j] = (unsigned)r * (unsigned)Npad * 2u + (unsigned)(((lane & 7) ^ bw_swz(r)) << 4);
+    voff_t[j] = (unsigned)r * (unsigned)Npad * 2u + (unsigned)(((lane & 7) ^ lds_swz_row<4>(r)) << 4);
   }
   auto stage = [&](int t, int slot) {
     const unsigned base = smem_u + slot * DK_STAGE;
 #pragma unroll
     for (int j = 0; j < PPW; ++j) {
       const int p = wave * PPW + j;
-      bw_dma16(voff, qf_b + (size_t)t * 8192 + p * 1024, base + DK_QF + p * 1024);
-      bw_dma16(voff, dof_b + (size_t)t * 8192 + p * 1024, base + DK_DOF + p * 1024);
-      bw_dma16(voff_t[j], qt_b + (size_t)t * 128, base + DK_QT + p * 1024);
-      bw_dma16(voff_t[j], dot_b + (size_t)t * 128, base + DK_DOT + p * 1024);
+      lds_dma16(voff, qf_b + (size_t)t * 8192 + p * 1024, base + DK_QF + p * 1024);
+      lds_dma16(voff, dof_b + (size_t)t * 8192 + p * 1024, base + DK_DOF + p * 1024);
+      lds_dma16(voff_t[j], qt_b + (size_t)t * 128, base + DK_QT + p * 1024);
+      lds_dma16(voff_t[j], dot_b + (size_t)t * 128, base + DK_DOT + p * 1024);
     }
-    if (wave == 0) bw_dma4(lane * 4, l2_b + (size_t)t * 256, base + DK_ST);
-    if (wave == 1) bw_dma4(lane * 4, dl_b + (size_t)t * 256, base + DK_ST + 256);
+    if (wave == 0) lds_dma4(lane * 4, l2_b + (size_t)t * 256, base + DK_ST);
+    if (wave == 1) lds_dma4(lane * 4, dl_b + (size_t)t * 256, base + DK_ST + 256);
   };
   auto ring_barrier = [&]() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -697,7 +687,7 @@ __global__ __launch_bounds__(64 * NW, 2) void sdpa_bwd_dkv_dma_kernel(const __bf
 
   const int nqt = Npad / BW_TILE;
   const int prow = pi_row(li);
-  const int sw = bw_swz(li);
+  const int sw = lds_swz_row<4>(li);
   int off_t[4];                              // [qb * 2 + s2]: byte offset of this lane's chunk in row li of a transposed tile
 #pragma unroll
   for (int c2 = 0; c2 < 4; ++c2) off_t[c2] = li * 128 + (((c2 * 2 + half) ^ sw) << 4);
@@ -856,7 +846,7 @@ __global__ __launch_bounds__(64 * NW, AS_BWD_DQ_OCC) void sdpa_bwd_dq_dma_kernel
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(fq[nq][0].v), "+v"(fq[nq][1].v), "+v"(fq[nq][2].v), "+v"(fq[nq][3].v), "+v"(fdo[nq][0].v),
                  "+v"(fdo[nq][1].v), "+v"(fdo[nq][2].v), "+v"(fdo[nq][3].v), "+v"(lse2[nq]), "+v"(dl[nq]));
 
-  const unsigned smem_u = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem;
+  const unsigned smem_u = lds_addr(smem);
   const char* k_b = reinterpret_cast<const char*>(k + (size_t)bh * Npad * BW_HD);
   const char* v_b = reinterpret_cast<const char*>(vrow + (size_t)bh * Npad * BW_HD);
   const char* kt_b = reinterpret_cast<const char*>(kt + (size_t)bh * BW_HD * Npad);
@@ -864,7 +854,7 @@ __global__ __launch_bounds__(64 * NW, AS_BWD_DQ_OCC) void sdpa_bwd_dq_dma_kernel
 #pragma unroll
   for (int j = 0; j < PPW; ++j) {
     const int r = (wave * PPW + j) * 8 + (lane >> 3);
-    const unsigned ch = (unsigned)(((lane & 7) ^ bw_swz(r)) << 4);
+    const unsigned ch = (unsigned)(((lane & 7) ^ lds_swz_row<4>(r)) << 4);
     voff_r[j] = (unsigned)r * 128u + ch;
     voff_t[j] = (unsigned)r * (unsigned)Npad * 2u + ch;
   }
@@ -873,9 +863,9 @@ __global__ __launch_bounds__(64 * NW, AS_BWD_DQ_OCC) void sdpa_bwd_dq_dma_kernel
 #pragma unroll
     for (int j = 0; j < PPW; ++j) {
       const int p = wave * PPW + j;
-      bw_dma16(voff_r[j], k_b + (size_t)t * 8192, base + DQ_K + p * 1024);
-      bw_dma16(voff_r[j], v_b + (size_t)t * 8192, base + DQ_V + p * 1024);
-      bw_dma16(voff_t[j], kt_b + (size_t)t * 128, base + DQ_KT + p * 1024);
+      lds_dma16(voff_r[j], k_b + (size_t)t * 8192, base + DQ_K + p * 1024);
+      lds_dma16(voff_r[j], v_b + (size_t)t * 8192, base + DQ_V + p * 1024);
+      lds_dma16(voff_t[j], kt_b + (size_t)t * 128, base + DQ_KT + p * 1024);
     }
   };
   auto ring_barrier = [&]() {
@@ -894,7 +884,7 @@ __global__ __launch_bounds__(64 * NW, AS_BWD_DQ_OCC) void sdpa_bwd_dq_dma_kernel
   const int prow = pi_row(li);
   int off_k[4], off_t[4];                    // [ks] in row prow of a row-major tile / [kb * 2 + s2] in row li of the K^T tile
   {
-    const int swp = bw_swz(prow), swl = bw_swz(li);
+    const int swp = lds_swz_row<4>(prow), swl = lds_swz_row<4>(li);
 #pragma unroll
     for (int c2 = 0; c2 < 4; ++c2) {
       off_k[c2] = prow * 128 + (((c2 * 2 + half) ^ swp) << 4);
@@ -985,36 +975,32 @@ __global__ __launch_bounds__(64 * NW, AS_BWD_DQ_OCC) void sdpa_bwd_dq_dma_kernel
 // the L2 -> LDS bytes, no strided 128-byte rows at stride 2 Npad, a 4-deep ring in the LDS of the old 2-deep one -- the
 // PMC profile of the old kernels shows waves waiting 58 % (dK/dV) of their time, the MFMA pipe busy 32 %: each iteration
 // cost one exposed DMA latency.  The prep kernel no longer writes q^T, k^T, dO^T.
-//   image of a 64-row x 128-byte tile: row r at r * 128, its 16-byte chunk c at position c ^ t3_swz(r) (swizzled on the
-//   DMA's source address).  t3_swz makes both access patterns bank-conflict-free: the ds_read_b128 row fragments (16-lane
+//   image of a 64-row x 128-byte tile: row r at r * 128, its 16-byte chunk c at position c ^ lds_swz_tr(r) (swizzled on the
+//   DMA's source address).  lds_swz_tr makes both access patterns bank-conflict-free: the ds_read_b128 row fragments (16-lane
 //   service groups over rows {0-3,12-15,20-27} / {4-11,16-19,28-31}: the eight rows of one parity get eight distinct
 //   positions) and the transposing reads (a 32-lane group covers 4 rows x 4 chunks: rows r, r + 2 land in different halves
 //   of the 128-byte line).
 // A row's sums run over the same tiles in the same order with the same operand values: bitwise the results of the kernels
 // above.
 // ---------------------------------------------------------------------------------------------------------
-typedef short bw_i16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ int t3_swz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
-// transposed fragment (lds_frag_tr3 below): lane (li, half) gets rows [8 half .. 8 half + 7] of column li of a 16-row x
-// 32-column block from two reads (rows +0..3, rows +4..7)
+// lds_swz_tr, lds_ptr, the transposed fragment loader lds_frag_tr and static_for: lds_asm.h
 template <int CNT> __device__ __forceinline__ void bw_wait_newer(int newer) {       // my DMAs of all but `newer` tiles have landed
   if (newer >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * CNT) : "memory");
   else if (newer == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
-typedef __attribute__((address_space(3))) const char* bw_lds_ptr;       // 32-bit LDS pointers: lane pointer + constant folds into the DS immediate
 struct T3Lane {                              // per-lane pointers into slot 0's first tile image
-  bw_lds_ptr pa[4];                          // [ks]: row pi(li), chunk 2 ks + half (add 4096 for the second 32-row block)
-  bw_lds_ptr pt[2][2];                       // [db][q]: transposing read of rows 4 q .. 4 q + 3 of a 16-row group, columns 32 db .. (add 4096 qb + 2048 s2)
-  bw_lds_ptr pst;                            // my 8-row run of the row statistics (dK/dV kernel)
+  lds_ptr pa[4];                             // [ks]: row pi(li), chunk 2 ks + half (add 4096 for the second 32-row block)
+  lds_ptr pt[2][2];                          // [db][q]: transposing read of rows 4 q .. 4 q + 3 of a 16-row group, columns 32 db .. (add 4096 qb + 2048 s2)
+  lds_ptr pst;                               // my 8-row run of the row statistics (dK/dV kernel)
   unsigned voff[2];                          // DMA source offsets of my two 8-row pieces (row-major source, 128-byte rows)
 };
 __device__ __forceinline__ T3Lane t3_lane(const char* smem, int lane, int wave) {
   T3Lane L;
-  const bw_lds_ptr base = (bw_lds_ptr)smem;
+  const lds_ptr base = (lds_ptr)smem;
   const int li = lane & 31, half = lane >> 5, prow = pi_row(li);
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) L.pa[ks] = base + (prow * 128 + (((2 * ks + half) ^ t3_swz(prow)) << 4));
+  for (int ks = 0; ks < 4; ++ks) L.pa[ks] = base + (prow * 128 + (((2 * ks + half) ^ lds_swz_tr(prow)) << 4));
   const int g = lane >> 4, tt = lane & 15;
   const int rl = 8 * (g >> 1) + (tt >> 2), cl = 2 * (g & 1) + ((tt & 3) >> 1);
 #pragma unroll
@@ -1022,25 +1008,18 @@ __device__ __forceinline__ T3Lane t3_lane(const char* smem, int lane, int wave) 
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int r = rl + 4 * q, c = 4 * db + cl;
-      L.pt[db][q] = base + (r * 128 + ((c ^ t3_swz(r)) << 4) + (tt & 1) * 8);
+      L.pt[db][q] = base + (r * 128 + ((c ^ lds_swz_tr(r)) << 4) + (tt & 1) * 8);
     }
   L.pst = base + (16384 + 32 * half);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int r = (wave * 2 + j) * 8 + (lane >> 3);
-    L.voff[j] = (unsigned)(r * 128 + (((lane & 7) ^ t3_swz(r)) << 4));
+    L.voff[j] = (unsigned)(r * 128 + (((lane & 7) ^ lds_swz_tr(r)) << 4));
   }
   return L;
 }
-__device__ __forceinline__ void lds_frag3(Frag<__bf16>& f, bw_lds_ptr p) {
+__device__ __forceinline__ void lds_frag3(Frag<__bf16>& f, lds_ptr p) {
   f.v = *reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(p);
-}
-__device__ __forceinline__ void lds_frag_tr3(Frag<__bf16>& f, bw_lds_ptr p0, bw_lds_ptr p1) {
-  const bw_i16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bw_i16x4*)p0);
-  const bw_i16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bw_i16x4*)p1);
-  typedef short i16x8 __attribute__((ext_vector_type(8)));
-  const i16x8 w = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  f.v = __builtin_bit_cast(bf16x8, w);
 }
 
 constexpr int T3_A = 0, T3_B = 8192, T3_ST = 16384;
@@ -1064,14 +1043,8 @@ __device__ __forceinline__ unsigned t3_pack(float a, float b) {      // two fp32
   return r;
 }
 __device__ __forceinline__ void t3_frag_words(Frag<__bf16>& f, unsigned a, unsigned b, unsigned c, unsigned d) {
-  const bw_u32x4 w = {a, b, c, d};
+  const u32x4 w = {a, b, c, d};
   f.v = __builtin_bit_cast(bf16x8, w);
-}
-template <typename F, int... Is> __device__ __forceinline__ void t3_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, typename F> __device__ __forceinline__ void t3_static_for(F&& f) {
-  t3_static_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 #ifndef AS_BWD_PRIO
 #define AS_BWD_PRIO 0                        // 1: s_setprio 1 around the MFMA phases (experiments)
@@ -1118,7 +1091,7 @@ __global__ __launch_bounds__(BW_NT, 2) void sdpa_bwd_dkv_tr_kernel(const __bf16*
   }
   // (these ordinary loads are waited for BEHIND the first tiles' LDS-DMA below: one round trip instead of two)
 
-  const unsigned smem_u = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem;
+  const unsigned smem_u = lds_addr(smem);
   const char* q_b = reinterpret_cast<const char*>(qr + (size_t)bh * Npad * BW_HD);
   const char* do_b = reinterpret_cast<const char*>(dor + (size_t)bh * Npad * BW_HD);
   const char* l2_b = reinterpret_cast<const char*>(nlse2 + (size_t)bh * Npad);
@@ -1129,11 +1102,11 @@ __global__ __launch_bounds__(BW_NT, 2) void sdpa_bwd_dkv_tr_kernel(const __bf16*
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int p = wave * 2 + j;
-      bw_dma16(L.voff[j], q_b + (size_t)t * 8192, base + T3_A + p * 1024);
-      bw_dma16(L.voff[j], do_b + (size_t)t * 8192, base + T3_B + p * 1024);
+      lds_dma16(L.voff[j], q_b + (size_t)t * 8192, base + T3_A + p * 1024);
+      lds_dma16(L.voff[j], do_b + (size_t)t * 8192, base + T3_B + p * 1024);
     }
-    if (wave == 0) bw_dma4(lane * 4, l2_b + (size_t)t * 256, base + T3_ST);
-    if (wave == 1) bw_dma4(lane * 4, dl_b + (size_t)t * 256, base + T3_ST + 256);
+    if (wave == 0) lds_dma4(lane * 4, l2_b + (size_t)t * 256, base + T3_ST);
+    if (wave == 1) lds_dma4(lane * 4, dl_b + (size_t)t * 256, base + T3_ST + 256);
   };
 
   f32x16 dkacc[2], dvacc[2];
@@ -1152,7 +1125,7 @@ __global__ __launch_bounds__(BW_NT, 2) void sdpa_bwd_dkv_tr_kernel(const __bf16*
   // the ring slot is a compile-time constant inside the body (NST tiles per trip): every LDS address is a loop-invariant
   // lane offset + an immediate
   for (int t0 = 0; t0 < nqt; t0 += NST) {
-    t3_static_for<NST>([&](auto slot_c) {
+    static_for<NST>([&](auto slot_c) {
     constexpr int SLOT = decltype(slot_c)::value;
     const int t = t0 + SLOT;
     if (t >= nqt) return;
@@ -1188,8 +1161,8 @@ __global__ __launch_bounds__(BW_NT, 2) void sdpa_bwd_dkv_tr_kernel(const __bf16*
 #pragma unroll
         for (int db = 0; db < 2; ++db) {
           const int o = QO + qb * 4096 + s2 * 2048;
-          lds_frag_tr3(tdo[db][s2], L.pt[db][0] + (o + T3_B), L.pt[db][1] + (o + T3_B));
-          lds_frag_tr3(tq[db][s2], L.pt[db][0] + o, L.pt[db][1] + o);
+          lds_frag_tr(tdo[db][s2], L.pt[db][0] + (o + T3_B), L.pt[db][1] + (o + T3_B));
+          lds_frag_tr(tq[db][s2], L.pt[db][0] + o, L.pt[db][1] + o);
         }
       t3_prio(0);
       __builtin_amdgcn_sched_barrier(0);
@@ -1268,7 +1241,7 @@ __global__ __launch_bounds__(BW_NT, 2) void sdpa_bwd_dq_tr_kernel(const __bf16* 
   float ndl = ndelta[(size_t)bh * Npad + qc];
   // (waited for behind the first tiles' LDS-DMA below: one round trip instead of two)
 
-  const unsigned smem_u = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem;
+  const unsigned smem_u = lds_addr(smem);
   const char* k_b = reinterpret_cast<const char*>(kr + (size_t)bh * Npad * BW_HD);
   const char* v_b = reinterpret_cast<const char*>(vrow + (size_t)bh * Npad * BW_HD);
   const T3Lane L = t3_lane(smem, lane, wave);
@@ -1277,8 +1250,8 @@ __global__ __launch_bounds__(BW_NT, 2) void sdpa_bwd_dq_tr_kernel(const __bf16* 
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int p = wave * 2 + j;
-      bw_dma16(L.voff[j], k_b + (size_t)t * 8192, base + T3_A + p * 1024);
-      bw_dma16(L.voff[j], v_b + (size_t)t * 8192, base + T3_B + p * 1024);
+      lds_dma16(L.voff[j], k_b + (size_t)t * 8192, base + T3_A + p * 1024);
+      lds_dma16(L.voff[j], v_b + (size_t)t * 8192, base + T3_B + p * 1024);
     }
   };
 
@@ -1297,7 +1270,7 @@ __global__ __launch_bounds__(BW_NT, 2) void sdpa_bwd_dq_tr_kernel(const __bf16* 
 #pragma unroll
   for (int r = 0; r < 16; ++r) { c_l[r] = nl2; c_d[r] = ndl; }
   for (int t0 = 0; t0 < nkt; t0 += NST) {
-    t3_static_for<NST>([&](auto slot_c) {
+    static_for<NST>([&](auto slot_c) {
     constexpr int SLOT = decltype(slot_c)::value;
     const int t = t0 + SLOT;
     if (t >= nkt) return;
@@ -1330,7 +1303,7 @@ __global__ __launch_bounds__(BW_NT, 2) void sdpa_bwd_dq_tr_kernel(const __bf16* 
 #pragma unroll
           for (int db = 0; db < 2; ++db) {
             const int o = KO + kb * 4096 + s2 * 2048;
-            lds_frag_tr3(tk[db][s2], L.pt[db][0] + o, L.pt[db][1] + o);
+            lds_frag_tr(tk[db][s2], L.pt[db][0] + o, L.pt[db][1] + o);
           }
         if (kb == 0) t3_rows<KO + 4096>(R, L);
         t3_prio(0);

@@ -15,6 +15,7 @@
 // as fp32 and are read as broadcasts; all arithmetic is fp32 (the softmax in exp(x - max) / sum form, as torch's).
 // bf16 tensors: window_attn_mfma_kernel below (both products on v_mfma_f32_32x32x16_bf16, fp32 softmax).
 #include "common.h"
+#include "lds_asm.h"
 
 namespace {
 
@@ -526,16 +527,7 @@ __global__ __launch_bounds__(64) void window_attn_bwd_kernel(const T* __restrict
 #ifndef AS_WA_ABLATE
 #define AS_WA_ABLATE 0                       // (timing experiments: 1 no table-gradient loop, 2 no dqkv stores, 3 no table loads)
 #endif
-typedef short wa_i16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) const char* wa_lds_ptr;
-__device__ __forceinline__ int wa_swz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }      // sdpa_bwd.hip t3_swz
-__device__ __forceinline__ void wa_frag_tr(Frag<__bf16>& f, wa_lds_ptr p0, wa_lds_ptr p1) {
-  const wa_i16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wa_i16x4*)p0);
-  const wa_i16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wa_i16x4*)p1);
-  typedef short i16x8 __attribute__((ext_vector_type(8)));
-  const i16x8 w = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  f.v = __builtin_bit_cast(bf16x8, w);
-}
+// transposing-read fragments (lds_frag_tr) and the chunk swizzle of the 128-byte-row images (lds_swz_tr): lds_asm.h
 
 template <int WS, int HD>
 __global__ __launch_bounds__(256, 2) void window_attn_bwd_mfma_kernel(const __bf16* __restrict__ qkv, const float* __restrict__ bqkv,
@@ -690,7 +682,7 @@ __global__ __launch_bounds__(256, 2) void window_attn_bwd_mfma_kernel(const __bf
   auto put_image = [&](f32x16 (&src)[2][2]) {
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib) {
-      const int qrow = ib * 32 + li, sw = wa_swz(qrow);
+      const int qrow = ib * 32 + li, sw = lds_swz_tr(qrow);
 #pragma unroll
       for (int jb = 0; jb < 2; ++jb)
 #pragma unroll
@@ -710,7 +702,7 @@ __global__ __launch_bounds__(256, 2) void window_attn_bwd_mfma_kernel(const __bf
   // per-lane pieces of the transposing reads (16-lane group g_ = lane >> 4, t_ = lane & 15): row t_ >> 2 of the 4-row group,
   // columns 16 (g_ & 1) + 4 (t_ & 3) .. +3
   const int g_ = lane >> 4, t_ = lane & 15;
-  const wa_lds_ptr Rm3 = (wa_lds_ptr)Rm, Im3 = (wa_lds_ptr)Im;
+  const lds_ptr Rm3 = (lds_ptr)Rm, Im3 = (lds_ptr)Im;
   const int rm_lane = (t_ >> 2) * 64 + (16 * (g_ & 1) + 4 * (t_ & 3)) * 2;      // inside a row-major [token][32] image
 
   // dQ^T[c][query] = K^T . dS^T: A = K^T (rows c, keys in acc_row's order: key0 .. +3 and key0 + 8 .. +11), B = dS^T in place
@@ -725,7 +717,7 @@ __global__ __launch_bounds__(256, 2) void window_attn_bwd_mfma_kernel(const __bf
     for (int s = 0; s < 2; ++s) {
       const int key0 = jb * 32 + 16 * s + 4 * hf;
       Frag<__bf16> fa;
-      wa_frag_tr(fa, Rm3 + (key0 * 64 + rm_lane), Rm3 + ((key0 + 8) * 64 + rm_lane));
+      lds_frag_tr(fa, Rm3 + (key0 * 64 + rm_lane), Rm3 + ((key0 + 8) * 64 + rm_lane));
 #pragma unroll
       for (int ib = 0; ib < 2; ++ib) {
         Frag<__bf16> fb;
@@ -745,14 +737,14 @@ __global__ __launch_bounds__(256, 2) void window_attn_bwd_mfma_kernel(const __bf
     for (int kq = 0; kq < 4; ++kq) {
       const int q0 = 16 * kq + 8 * hf;                                // + 4 q' + (t_ >> 2): the row this lane addresses
       Frag<__bf16> fa;
-      wa_frag_tr(fa, Rm3 + (q0 * 64 + rm_lane), Rm3 + ((q0 + 4) * 64 + rm_lane));
+      lds_frag_tr(fa, Rm3 + (q0 * 64 + rm_lane), Rm3 + ((q0 + 4) * 64 + rm_lane));
 #pragma unroll
       for (int jb = 0; jb < 2; ++jb) {
         // B fragments from the [query][key] image: rows q0 + 4 q' + (t_ >> 2), key columns 32 jb + 16 (g_ & 1) + 4 (t_ & 3) .. +3
         const int chunk = 4 * jb + 2 * (g_ & 1) + ((t_ & 3) >> 1), sub = 8 * (t_ & 1);
         const int r0 = q0 + (t_ >> 2), r1 = r0 + 4;
         Frag<__bf16> fb;
-        wa_frag_tr(fb, Im3 + (r0 * 128 + ((chunk ^ wa_swz(r0)) << 4) + sub), Im3 + (r1 * 128 + ((chunk ^ wa_swz(r1)) << 4) + sub));
+        lds_frag_tr(fb, Im3 + (r0 * 128 + ((chunk ^ lds_swz_tr(r0)) << 4) + sub), Im3 + (r1 * 128 + ((chunk ^ lds_swz_tr(r1)) << 4) + sub));
         out[jb] = mma32(fa, fb, out[jb]);
       }
     }
@@ -783,7 +775,7 @@ __global__ __launch_bounds__(256, 2) void window_attn_bwd_mfma_kernel(const __bf
         for (int bi = 0; bi < WS; ++bi) {
           const int bj = min(max(bi - db, 0), WS - 1);
           const int i = ai * WS + bi, j = (ai - da) * WS + bj;
-          v[bi] = (float)*reinterpret_cast<const __bf16*>(Di + i * 128 + (((j >> 3) ^ wa_swz(i)) << 4) + (j & 7) * 2);
+          v[bi] = (float)*reinterpret_cast<const __bf16*>(Di + i * 128 + (((j >> 3) ^ lds_swz_tr(i)) << 4) + (j & 7) * 2);
         }
 #pragma unroll
         for (int bi = 0; bi < WS; ++bi) sum += (bi - db >= 0 && bi - db < WS) ? v[bi] : 0.0f;

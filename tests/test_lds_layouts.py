@@ -1,5 +1,6 @@
-"""Host-side check of the LDS tile layouts the round-4 kernels rely on (csrc/sdpa_bwd.hip `t3_swz`, csrc/window_attn.hip
-`wa_swz`, csrc/gemm_tn.hip's 256 x 128 tile): the per-lane byte addresses of every access pattern are recomputed here from the
+"""Host-side check of the LDS tile layouts the round-4 kernels rely on (csrc/lds_asm.h `lds_swz_tr`, shared by
+csrc/sdpa_bwd.hip and csrc/window_attn.hip and called `t3_swz` / `wa_swz` below; `g_swz<4>` below is `lds_swz_row<4>` of the
+same header; csrc/gemm_tn.hip's 256 x 128 tile): the per-lane byte addresses of every access pattern are recomputed here from the
 formulas in the kernels' comments, and every group of lanes the LDS services in one cycle (MI355X_MICROARCH.md "LDS": ds_read_b128
 in 16-lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31} / +32, ds_read_b64(_tr_b16) in 32-lane groups, 64 banks of 4 bytes) must
 touch 64 distinct banks -- the property the PMC counter SQ_LDS_BANK_CONFLICT = 0 confirmed on the device."""
