@@ -1,7 +1,6 @@
 // Shared device/host helpers for libattnshift_hip.so (gfx950 / CDNA4 only).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,83 +33,6 @@ void as_set_error(const char* fmt, ...);
 static inline int as_ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int as_round_up(int a, int b) { return as_ceil_div(a, b) * b; }
 
-// ---------------------------------------------------------------------------------------------
-// Fork / join onto a helper stream inside one C call: two independent launch chains of a backward pass run side by side
-// (a chain of one-workgroup-per-CU split-K products leaves most of every CU free; two half-empty last rounds fill each
-// other's slots).  The caller's stream forks with an event, the helper chain runs on the side stream, and the caller's
-// stream waits for the helper's last launch before the call returns -- so the caller sees ordinary stream order.
-// One set of stream + events per host thread, device and slot (nested users take different slots).  AS_BWD_SERIAL=1 (read
-// once) keeps everything on the caller's stream.
-// ---------------------------------------------------------------------------------------------
-struct AsSide {
-  // one stream + three events PER DEVICE (a thread alternating between devices reuses each device's set instead of
-  // re-creating -- and leaking -- one on every switch); a set whose creation fails half-way is destroyed and stays off
-  static constexpr int kMaxDev = 16;
-  struct Slot {
-    hipStream_t st = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr, mid = nullptr;
-    int state = 0;                                      // 0 = not tried, 1 = ready, -1 = failed (do not retry)
-  };
-  Slot slots[kMaxDev];
-  hipStream_t st = nullptr;                             // the CURRENT device's set (valid while ok)
-  hipEvent_t fork = nullptr, join = nullptr, mid = nullptr;
-  bool ok = false;
-  void init() {
-    int d = -1;
-    ok = false;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDev) return;
-    Slot& sl = slots[d];
-    if (sl.state == 0) {
-      const bool made = hipStreamCreateWithFlags(&sl.st, hipStreamNonBlocking) == hipSuccess &&
-                        hipEventCreateWithFlags(&sl.fork, hipEventDisableTiming) == hipSuccess &&
-                        hipEventCreateWithFlags(&sl.join, hipEventDisableTiming) == hipSuccess &&
-                        hipEventCreateWithFlags(&sl.mid, hipEventDisableTiming) == hipSuccess;
-      if (!made) {
-        if (sl.mid) (void)hipEventDestroy(sl.mid);
-        if (sl.join) (void)hipEventDestroy(sl.join);
-        if (sl.fork) (void)hipEventDestroy(sl.fork);
-        if (sl.st) (void)hipStreamDestroy(sl.st);
-        sl = Slot();
-        (void)hipGetLastError();                        // the caller falls back to its own stream: not its error
-      }
-      sl.state = made ? 1 : -1;
-    }
-    if (sl.state != 1) return;
-    st = sl.st; fork = sl.fork; join = sl.join; mid = sl.mid;
-    ok = true;
-  }
-  // thread exit (the instances are thread_local): give the streams and events back.  Errors are ignored -- at process exit
-  // the HIP runtime may already be gone.
-  ~AsSide() {
-    for (Slot& sl : slots) {
-      if (sl.state != 1) continue;
-      (void)hipEventDestroy(sl.mid);
-      (void)hipEventDestroy(sl.join);
-      (void)hipEventDestroy(sl.fork);
-      (void)hipStreamDestroy(sl.st);
-      sl = Slot();
-    }
-    (void)hipGetLastError();
-  }
-};
-static inline bool as_side_serial() {
-  static const bool serial = getenv("AS_BWD_SERIAL") != nullptr;
-  return serial;
-}
-// -> the stream the helper chain should use: the side stream behind an event of `s`, or `s` itself (serial / no stream)
-static inline hipStream_t as_side_fork(AsSide& sd, hipStream_t s) {
-  if (as_side_serial()) return s;
-  sd.init();
-  if (sd.ok && hipEventRecord(sd.fork, s) == hipSuccess && hipStreamWaitEvent(sd.st, sd.fork, 0) == hipSuccess) return sd.st;
-  return s;
-}
-// `to` waits for everything queued on `from` so far (no-op when they are the same stream)
-static inline void as_side_wait(AsSide& sd, hipEvent_t ev, hipStream_t from, hipStream_t to) {
-  if (from == to) return;
-  if (hipEventRecord(ev, from) != hipSuccess || hipStreamWaitEvent(to, ev, 0) != hipSuccess)
-    (void)hipStreamSynchronize(from);                   // (a lost device; keeps the order safe)
-}
-static inline void as_side_join(AsSide& sd, hipStream_t sq, hipStream_t s) { as_side_wait(sd, sd.join, sq, s); }
 #ifdef __HIPCC__
 __device__ __forceinline__ int as_ceil_div_dev(int a, int b) { return (a + b - 1) / b; }
 #endif

@@ -22,6 +22,7 @@
 // sinking the loads to their uses.
 #include "common.h"
 #include "bilinear.h"
+#include "launch.h"
 
 namespace {
 
@@ -915,8 +916,7 @@ extern "C" int as_refine_similarity(const float* feat, const float* seeds, const
   char* w = (char*)ws;
   float* work = (float*)(w + L.work);
   unsigned* peak = (unsigned*)(w + L.peak);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)refine_aggregate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  as_lds_optin<refine_aggregate_kernel>(lds);
 
   // (the per-map peaks feed the aggregation of the NEXT level only: without refinement levels nothing reads them)
   if (refine_times > 0) (void)hipMemsetAsync(peak, 0, (size_t)2 * PMAX * 4, s);

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "gemm_epi.h"
 #include "lds_asm.h"
+#include "launch.h"
 
 namespace {
 
@@ -723,11 +724,7 @@ int launch_gemm_glds_wm(const void* A, const void* W, const float* bias, void* o
   dim3 grid(8 * as_ceil_div(tiles, 8), MODE == 3 ? as_ceil_div(K, epi.N) : 1);   // x padded to a multiple of the 8 XCDs (tile order)
   // ring 48 / 72 / 96 KiB; the epilogue restages the output tile in the same memory (35 / 70 / 133 KiB)
   const size_t lds = (size_t)GT::LDS;
-  static std::atomic<bool> attr_set{false};   // (idempotent attribute call: a race only repeats it)
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_glds_kernel<MODE, WM, WN, RI, KS, NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  as_lds_optin<gemm_glds_kernel<MODE, WM, WN, RI, KS, NJ>>(lds);
   hipLaunchKernelGGL((gemm_glds_kernel<MODE, WM, WN, RI, KS, NJ>), grid, dim3(GT::NT_), lds, s, (const __bf16*)A, (const __bf16*)W, bias,
                      (__bf16*)out, M, Nout, K, act, epi);
   AS_CHECK_LAUNCH("gemm_glds");
@@ -789,11 +786,7 @@ int launch_gemm_glds(const void* A, const void* W, const float* bias, void* out,
 struct SkPlan { int pick, tiles, S; size_t part_bytes, total; bool use; };
 SkPlan sk_plan(int M, int Nout, int K, bool qkv) {
   SkPlan p{};
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
+  const int cus = as_cu_count();
   p.S = cus - cus % 8;                                   // (ranks are dealt per XCD: a multiple of 8)
   const bool wide = !qkv && Nout >= 1024 && K % 64 == 0; // the tile launch_gemm_glds would pick among the 1-per-CU ones
   p.pick = wide ? 4 : 3;
@@ -822,31 +815,23 @@ int launch_gemm_sk(const void* A, const void* W, const float* bias, void* out, i
   int* counters = (int*)(w + p.part_bytes);
   (void)hipMemsetAsync(counters, 0, (size_t)2 * p.tiles * sizeof(int), s);
   float* parts = (float*)w;
-  auto go = [&](auto kern, size_t lds, int nt) {
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(p.S), dim3(nt), lds, s, (const __bf16*)A, (const __bf16*)W, bias, (__bf16*)out, M, Nout, K, act, epi);
-  };
+#define AS_SK_GO(...)                                                                                                        \
+  do {                                                                                                                       \
+    using GT = GTile<__VA_ARGS__>;                                                                                           \
+    as_lds_optin<gemm_glds_kernel<4, __VA_ARGS__>>((size_t)GT::LDS);                                                         \
+    hipLaunchKernelGGL((gemm_glds_kernel<4, __VA_ARGS__>), dim3(p.S), dim3(GT::NT_), (size_t)GT::LDS, s, (const __bf16*)A,    \
+                       (const __bf16*)W, bias, (__bf16*)out, M, Nout, K, act, epi);                                          \
+  } while (0)
   // (the stream-K hand-off borrows the q / k pointer slots of the epilogue descriptor: MODE 4 has no QKV outputs; MODE 5
   //  carries them in epi.vt's neighbours -- see SkQkv below)
-  if (p.pick == 4) {
-    if constexpr (MODE == 4) {
-      epi.q = parts; epi.k = counters;
-      go(gemm_glds_kernel<4, 2, 4, 4, 4, 2>, (size_t)GTile<2, 4, 4, 4, 2>::LDS, GTile<2, 4, 4, 4, 2>::NT_);
-    } else {
-      return AS_E_UNSUPPORTED;
-    }
+  if constexpr (MODE == 4) {
+    epi.q = parts; epi.k = counters;
+    if (p.pick == 4) AS_SK_GO(2, 4, 4, 4, 2);
+    else AS_SK_GO(4, 2, 2, 4, 2);
   } else {
-    if constexpr (MODE == 4) {
-      epi.q = parts; epi.k = counters;
-      go(gemm_glds_kernel<4, 4, 2, 2, 4, 2>, (size_t)GTile<4, 2, 2, 4, 2>::LDS, GTile<4, 2, 2, 4, 2>::NT_);
-    } else {
-      return AS_E_UNSUPPORTED;
-    }
+    return AS_E_UNSUPPORTED;
   }
+#undef AS_SK_GO
   AS_CHECK_LAUNCH("gemm_sk");
   return AS_OK;
 }
@@ -930,11 +915,7 @@ static int pp_pick(int M, int Nout, int K, bool qkv, int act) {
   if (e != nullptr && e[0] == 'a') return !qkv && as_pp_applies(M, Nout, K, 0) ? 0 : -1;
   if (e != nullptr && e[0] == 'b') return as_pp_applies(M, Nout, K, 1) ? 1 : -1;
   if (!as_pp_applies(M, Nout, K, 1)) return -1;
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n >= 8 ? n - n % 8 : 8;
-  }();
+  const int n = as_cu_count(), cus = n >= 8 ? n - n % 8 : 8;
   const int panels = as_ceil_div(M, 256), nk = K / 64;
   const int tiles_b = panels * (Nout / 128);
   if (tiles_b < 64) return -1;

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "gemm_epi.h"
 #include "lds_asm.h"
+#include "launch.h"
 
 #ifndef AS_PP_PRIO
 #define AS_PP_PRIO 1     // s_setprio: 0 none, 1 raised around the MFMA cluster, 2 raised in the load segment
@@ -596,27 +597,31 @@ struct PPWorkspace {
 constexpr size_t PP_SLAB_BYTES = (size_t)256 * 32 * 512 * 16;   // G <= 256 workgroups x the 256 x 256 tile's 32 vectors per thread
 constexpr size_t PP_FLAG_BYTES = (size_t)256 * 8 * sizeof(unsigned);
 
-PPWorkspace* pp_workspace(hipStream_t s) {
+// -> the stream's slabs and flags with the NEXT launch's epoch (never 0), all taken under the lock; slabs == nullptr: whole tiles
+PPWorkspace pp_workspace(hipStream_t s) {
   static std::mutex mu;
   static std::map<std::pair<int, hipStream_t>, PPWorkspace> all;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  if (hipGetDevice(&dev) != hipSuccess) return {};
   std::lock_guard<std::mutex> lock(mu);
   auto it = all.find({dev, s});
-  if (it != all.end()) return it->second.slabs ? &it->second : nullptr;
-  PPWorkspace ws;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return nullptr; }
-  void* mem = nullptr;
-  if (hipMalloc(&mem, PP_SLAB_BYTES + PP_FLAG_BYTES) != hipSuccess) {
-    (void)hipGetLastError();
-    all[{dev, s}] = ws;                                       // (remembered: this stream stays with whole tiles)
-    return nullptr;
+  if (it == all.end()) {
+    PPWorkspace ws;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return {}; }
+    void* mem = nullptr;
+    if (hipMalloc(&mem, PP_SLAB_BYTES + PP_FLAG_BYTES) == hipSuccess) {
+      ws.slabs = mem;
+      ws.flags = reinterpret_cast<unsigned*>(static_cast<char*>(mem) + PP_SLAB_BYTES);
+      (void)hipMemsetAsync(ws.flags, 0, PP_FLAG_BYTES, s);
+    } else {
+      (void)hipGetLastError();                                // (remembered empty: this stream stays with whole tiles)
+    }
+    it = all.emplace(std::make_pair(dev, s), ws).first;
   }
-  ws.slabs = mem;
-  ws.flags = reinterpret_cast<unsigned*>(static_cast<char*>(mem) + PP_SLAB_BYTES);
-  (void)hipMemsetAsync(ws.flags, 0, PP_FLAG_BYTES, s);
-  return &(all[{dev, s}] = ws);
+  PPWorkspace& ws = it->second;
+  if (ws.slabs != nullptr && ++ws.epoch == 0u) ws.epoch = 1u;
+  return ws;
 }
 
 // AS_GEMM_PP_SK = 0: whole tiles only | 1: the stream-K tail wherever it applies | unset: where the round model below predicts a gain
@@ -641,11 +646,7 @@ bool pp_sk_pays(int cfg, int tiles, int grid, int nk, bool gelu) {
 template <int CFG, int EM, int ACT>
 int launch_pp(const void* A, const void* W, const float* bias, void* out, int M, int Nout, int K, PPEpi epi, hipStream_t s) {
   using C = PPCfg<CFG>;
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n >= 8 ? n - n % 8 : 8;
-  }();
+  const int n = as_cu_count(), cus = n >= 8 ? n - n % 8 : 8;
   const int tiles = as_ceil_div(M, C::BM) * (Nout / C::BN);
   const int grid = tiles >= cus ? cus : as_round_up(tiles, 8);
   const size_t lds = (size_t)C::NBUF * C::BUF;
@@ -655,28 +656,25 @@ int launch_pp(const void* A, const void* W, const float* bias, void* out, int M,
   bool sk = false;
   if (tiles > grid && tiles % grid != 0 && grid <= 256 && !(EM == 0 && ACT == 3) && (long long)2 * grid * (K / 64) * grid < (1LL << 31) &&
       (pp_sk_mode() == 1 || (pp_sk_mode() < 0 && pp_sk_pays(CFG, tiles, grid, K / 64, EM != 1 && (ACT == 1 || ACT == 2))))) {
-    if (PPWorkspace* ws = pp_workspace(s)) {
+    const PPWorkspace ws = pp_workspace(s);
+    if (ws.slabs != nullptr) {
       plan.D = tiles / grid - 1;
       plan.sk_tiles = tiles - plan.D * grid;
-      if (++ws->epoch == 0u) ws->epoch = 1u;
-      plan.epoch = ws->epoch;
-      plan.slabs = ws->slabs;
-      plan.flags = ws->flags;
+      plan.epoch = ws.epoch;
+      plan.slabs = ws.slabs;
+      plan.flags = ws.flags;
       sk = true;
     }
   }
-  static std::atomic<bool> attr_set[2] = {{false}, {false}};
-  if (!attr_set[sk]) {
-    if (sk) (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<CFG, EM, ACT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    else (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<CFG, EM, ACT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[sk] = true;
-  }
-  if (sk)
+  if (sk) {
+    as_lds_optin<gemm_pp_kernel<CFG, EM, ACT, true>>(lds);
     hipLaunchKernelGGL((gemm_pp_kernel<CFG, EM, ACT, true>), dim3(grid), dim3(512), lds, s, (const __bf16*)A, (const __bf16*)W, bias,
                        (__bf16*)out, M, Nout, K, epi, plan);
-  else
+  } else {
+    as_lds_optin<gemm_pp_kernel<CFG, EM, ACT, false>>(lds);
     hipLaunchKernelGGL((gemm_pp_kernel<CFG, EM, ACT, false>), dim3(grid), dim3(512), lds, s, (const __bf16*)A, (const __bf16*)W, bias,
                        (__bf16*)out, M, Nout, K, epi, plan);
+  }
   AS_CHECK_LAUNCH("gemm_pp");
   return AS_OK;
 }

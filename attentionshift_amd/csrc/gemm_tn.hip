@@ -16,6 +16,7 @@
 #include <utility>
 #include "common.h"
 #include "lds_asm.h"
+#include "launch.h"
 
 namespace {
 
@@ -474,11 +475,7 @@ int as_tn_dw(const void* dy, const void* x, void* dW, float* db, float* db_part,
   AS_REQUIRE(!db || db_part, AS_E_BADARG, "tn dW: db needs its partial buffer ([<= 32][Nout] floats)");
   if (tn_wide(Nout, K)) {
     const int tiles = (Nout / TW_N) * (K / TW_K);
-    static std::atomic<bool> attr_w{false};
-    if (!attr_w) {
-      (void)hipFuncSetAttribute((const void*)gemm_tn_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TW_NSTAGE * TW_STAGE_B);
-      attr_w = true;
-    }
+    as_lds_optin<gemm_tn_wide_kernel>((size_t)TW_NSTAGE * TW_STAGE_B);
     hipLaunchKernelGGL(gemm_tn_wide_kernel, dim3(8 * as_ceil_div(tiles, 8), S), dim3(TN_NT), (size_t)TW_NSTAGE * TW_STAGE_B, s,
                        (const __bf16*)dy, (const __bf16*)x, (float*)ws, db ? db_part : nullptr, M, Nout, K, chunk);
     AS_CHECK_LAUNCH("gemm_tn_wide");
@@ -486,18 +483,15 @@ int as_tn_dw(const void* dy, const void* x, void* dW, float* db, float* db_part,
   const int tiles = (Nout / TN_T) * (K / TN_T);
   static const int stages = [] { const char* e = getenv("AS_TN_STAGES"); return e && atoi(e) == 4 ? 4 : 3; }();   // (experiments: 4-deep ring, 2 workgroups per CU)
   const size_t lds = (size_t)stages * TN_STAGE_B;
-  static std::atomic<bool> attr{false};
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_splitk_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TN_STAGE_B);
-    (void)hipFuncSetAttribute((const void*)gemm_tn_splitk_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * TN_STAGE_B);
-    attr = true;
-  }
-  if (stages == 3)
-    hipLaunchKernelGGL(gemm_tn_splitk_kernel<3>, dim3(8 * as_ceil_div(tiles, 8), S), dim3(TN_NT), lds, s, (const __bf16*)dy,
-                       (const __bf16*)x, (float*)ws, db ? db_part : nullptr, M, Nout, K, chunk);
-  else
+  if (stages == 4) {
+    as_lds_optin<gemm_tn_splitk_kernel<4>>(lds);
     hipLaunchKernelGGL(gemm_tn_splitk_kernel<4>, dim3(8 * as_ceil_div(tiles, 8), S), dim3(TN_NT), lds, s, (const __bf16*)dy,
                        (const __bf16*)x, (float*)ws, db ? db_part : nullptr, M, Nout, K, chunk);
+  } else {
+    as_lds_optin<gemm_tn_splitk_kernel<3>>(lds);
+    hipLaunchKernelGGL(gemm_tn_splitk_kernel<3>, dim3(8 * as_ceil_div(tiles, 8), S), dim3(TN_NT), lds, s, (const __bf16*)dy,
+                       (const __bf16*)x, (float*)ws, db ? db_part : nullptr, M, Nout, K, chunk);
+  }
   AS_CHECK_LAUNCH("gemm_tn_splitk");
   }
   const size_t n4 = (size_t)Nout * K / 4;

@@ -11,6 +11,7 @@
 // recomputed from the (L2-resident) 64x64 maps in each of three passes, so HBM traffic is the two
 // output tensors only.  Compiled with -ffp-contract=off so every step rounds like the ATen ops.
 #include "bilinear.h"
+#include "launch.h"
 
 namespace {
 
@@ -634,14 +635,7 @@ extern "C" int as_merge_parts(const float* prot, const uint8_t* keep, float thr,
              "as_merge_parts: P=%d prototypes per object (max %d), %d slots", P, MG_PMAX, slots);
   const size_t lds = (size_t)P * (C + 1) * sizeof(float);
   AS_REQUIRE(lds <= 140 * 1024, AS_E_UNSUPPORTED, "as_merge_parts: %d x %d prototypes exceed the LDS image", P, C);
-  // (a driver call in the latency-critical per-image chain: made only when this launch needs more than any before it; a race
-  //  between two host threads only repeats the idempotent call -- ADVICE r05)
-  static std::atomic<size_t> lds_set{48 * 1024};
-  if (lds > lds_set.load(std::memory_order_relaxed)) {
-    (void)hipFuncSetAttribute((const void*)merge_parts_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    size_t seen = lds_set.load(std::memory_order_relaxed);
-    while (seen < lds && !lds_set.compare_exchange_weak(seen, lds, std::memory_order_relaxed)) {}
-  }
+  as_lds_optin<merge_parts_kernel>(lds);                // (no driver call in this latency-critical per-image chain once granted)
   hipLaunchKernelGGL(merge_parts_kernel, dim3(G), dim3(MG_NT), lds, (hipStream_t)stream, prot, keep, thr, merged, ngroups, flag,
                      P, C, slots);
   AS_CHECK_LAUNCH("merge_parts");

@@ -11,6 +11,7 @@
 // bin (roi, ph, pw); the tensor-op form materialised [R, C, H, W] + [R, C, out*g, W] (several GB at 1024 RoIs x 768
 // channels).  The backward is a deterministic gather (below).
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -258,18 +259,15 @@ extern "C" int as_roi_align_bwd(const float* dout, const float* rois, float* dfe
   AS_REQUIRE(out_size * 2 * bsz <= RB_NT, AS_E_UNSUPPORTED, "as_roi_align_bwd: output size %d", out_size);
   const size_t lds = lds_of(bsz);
   AS_REQUIRE(lds <= 150 * 1024, AS_E_UNSUPPORTED, "as_roi_align_bwd: tables of a %dx%d map / output %d exceed LDS", H, W, out_size);
-  static std::atomic<bool> attr{false};
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)roi_align_bwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    (void)hipFuncSetAttribute((const void*)roi_align_bwd_kernel<RB_MAXPT>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    attr = true;
-  }
-  if (H * W <= RB_NT * 4)
+  if (H * W <= RB_NT * 4) {
+    as_lds_optin<roi_align_bwd_kernel<4>>(lds);
     hipLaunchKernelGGL(roi_align_bwd_kernel<4>, dim3(C / RB_CH, B), dim3(RB_NT), lds, (hipStream_t)stream, dout, rois, dfeat, B, H,
                        W, C, R, out_size, spatial_scale, sampling_ratio, aligned, bsz);
-  else
+  } else {
+    as_lds_optin<roi_align_bwd_kernel<RB_MAXPT>>(lds);
     hipLaunchKernelGGL(roi_align_bwd_kernel<RB_MAXPT>, dim3(C / RB_CH, B), dim3(RB_NT), lds, (hipStream_t)stream, dout, rois, dfeat,
                        B, H, W, C, R, out_size, spatial_scale, sampling_ratio, aligned, bsz);
+  }
   AS_CHECK_LAUNCH("roi_align_bwd");
   return AS_OK;
 }

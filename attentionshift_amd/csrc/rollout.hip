@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "lds_asm.h"
+#include "launch.h"
 
 namespace {
 
@@ -712,8 +713,7 @@ int launch_rollout_step2(const void* q, const void* k, const float* lse, const f
   AS_REQUIRE(lds <= 160 * 1024, AS_E_UNSUPPORTED, "rollout_step: LDS %zu B exceeds 160 KiB (h=%d)", lds, h);
 #define AS_RO2(HPW)                                                                                            \
   do {                                                                                                         \
-    (void)hipFuncSetAttribute((const void*)rollout_step2_kernel<T, HPW>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)lds);                                                                       \
+    as_lds_optin<rollout_step2_kernel<T, HPW>>(lds);                                                           \
     hipLaunchKernelGGL((rollout_step2_kernel<T, HPW>), grid, dim3(RO_NT), lds, s, (const T*)q, (const T*)k, lse, Rin, \
                        (const T*)rf_in, Rout, (T*)rf_out, part, B, N, Npad, h, Trows, nsplit, xbufs);          \
   } while (0)
@@ -726,11 +726,11 @@ int launch_rollout_step2(const void* q, const void* k, const float* lse, const f
     const int ks = rollout4_ksplit(B, N, h, 512);
     const size_t lds4 = (size_t)(Trows <= 32 ? R4Cfg<1>::NSTAGE : R4Cfg<4>::NSTAGE) * R4_STAGE;
     if (Trows <= 32) {
-      (void)hipFuncSetAttribute((const void*)rollout_step4_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
+      as_lds_optin<rollout_step4_kernel<1>>(lds4);
       hipLaunchKernelGGL(rollout_step4_kernel<1>, dim3(as_ceil_div(N, 128), B, ks * ng), dim3(RO_NT), lds4, s, (const __bf16*)q,
                          (const __bf16*)k, lse, (const __bf16*)rf_in, part, B, N, Npad, h, Trows, ks);
     } else {
-      (void)hipFuncSetAttribute((const void*)rollout_step4_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
+      as_lds_optin<rollout_step4_kernel<4>>(lds4);
       hipLaunchKernelGGL(rollout_step4_kernel<4>, dim3(as_ceil_div(N, 128), B, ks * ng), dim3(RO_NT), lds4, s, (const __bf16*)q,
                          (const __bf16*)k, lse, (const __bf16*)rf_in, part, B, N, Npad, h, Trows, ks);
     }
@@ -744,7 +744,7 @@ int launch_rollout_step2(const void* q, const void* k, const float* lse, const f
   if (sizeof(T) == 2 && h >= 8 && (getenv("AS_ROLLOUT_V2") == nullptr)) {
     // bf16, 8..16 heads (K tile 32..64 KiB): barrier-free kernel, LDS = K tile only
     const size_t lds3 = (size_t)h * 32 * Kj2<T>::PITCH;
-    (void)hipFuncSetAttribute((const void*)rollout_step3_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
+    as_lds_optin<rollout_step3_kernel<T>>(lds3);
     hipLaunchKernelGGL((rollout_step3_kernel<T>), grid, dim3(RO_NT), lds3, s, (const T*)q, (const T*)k, lse, Rin,
                        (const T*)rf_in, Rout, (T*)rf_out, part, B, N, Npad, h, Trows, nsplit);
   } else {

@@ -17,6 +17,7 @@
 #include <utility>
 #include "common.h"
 #include "lds_asm.h"
+#include "launch.h"
 
 namespace {
 
@@ -1289,15 +1290,7 @@ int sdpa_impl_forced() {
   return e ? atoi(e) : -1;
 }
 
-int sdpa_slots() {                                    // resident workgroups of sdpa_fwd_glds_kernel: 3 per CU
-  static int slots = 0;                               // read-only device-properties cache
-  if (slots == 0) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    slots = 3 * (cus > 0 ? cus : 256);
-  }
-  return slots;
-}
+int sdpa_slots() { return 3 * as_cu_count(); }       // resident workgroups of sdpa_fwd_glds_kernel: 3 per CU
 
 // key slices of a split q-tile: about one workgroup per CU, no empty slice
 int sdpa_tail_slices(int B, int N, int h) {
@@ -1436,60 +1429,11 @@ int launch_sdpa_glds(const void* q, const void* k, const void* vt, void* o, floa
   const size_t lds = (size_t)GL_NBUF * 2 * GL_TILE;        // 48 KiB
   // The split q-tile runs CONCURRENTLY with the main grid on a helper stream (fork / join with events on the caller's
   // stream): its 264 short workgroups fill the slots the main grid's workgroups free up as they retire, instead of
-  // running as a separate 13 us phase afterwards.  Helper stream and events are created once per host thread.
-  struct Side {                                          // one set PER DEVICE (as AsSide in common.h): a thread that alternates
-    enum { kMaxDev = 16 };                               // between devices reuses each device's set instead of leaking one per
-    struct Slot {                                        // switch; a set whose creation fails half-way is destroyed and stays off
-      hipStream_t st = nullptr, st2 = nullptr;
-      hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr;
-      int state = 0;                                     // 0 = not tried, 1 = ready, -1 = failed
-    };
-    Slot slots[kMaxDev];
-    hipStream_t st = nullptr, st2 = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr;
-    bool ok = false;
-    static void drop(Slot& sl) {
-      if (sl.join2) (void)hipEventDestroy(sl.join2);
-      if (sl.join) (void)hipEventDestroy(sl.join);
-      if (sl.fork) (void)hipEventDestroy(sl.fork);
-      if (sl.st2) (void)hipStreamDestroy(sl.st2);
-      if (sl.st) (void)hipStreamDestroy(sl.st);
-      sl = Slot();
-    }
-    void init() {
-      int d = -1;
-      ok = false;
-      if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDev) return;
-      Slot& sl = slots[d];
-      if (sl.state == 0) {
-        const bool made = hipStreamCreateWithFlags(&sl.st, hipStreamNonBlocking) == hipSuccess &&
-                          hipStreamCreateWithFlags(&sl.st2, hipStreamNonBlocking) == hipSuccess &&
-                          hipEventCreateWithFlags(&sl.fork, hipEventDisableTiming) == hipSuccess &&
-                          hipEventCreateWithFlags(&sl.join, hipEventDisableTiming) == hipSuccess &&
-                          hipEventCreateWithFlags(&sl.join2, hipEventDisableTiming) == hipSuccess;
-        if (!made) {
-          drop(sl);
-          (void)hipGetLastError();                       // the launch falls back to the caller's stream: not its error
-        }
-        sl.state = made ? 1 : -1;
-      }
-      if (sl.state != 1) return;
-      st = sl.st; st2 = sl.st2; fork = sl.fork; join = sl.join; join2 = sl.join2;
-      ok = true;
-    }
-    ~Side() {                                            // thread exit
-      for (Slot& sl : slots)
-        if (sl.state == 1) drop(sl);
-      (void)hipGetLastError();
-    }
-  };
-  static thread_local Side side;
-  if (ns > 0 || mixed) side.init();
-  const bool concurrent = ns > 0 && qtiles > 0 && side.ok && getenv("AS_SDPA_SERIAL") == nullptr;
-  hipStream_t s2 = concurrent ? side.st : s;
-  if (concurrent) {
-    if (hipEventRecord(side.fork, s) != hipSuccess || hipStreamWaitEvent(side.st, side.fork, 0) != hipSuccess) s2 = s;
-  }
+  // running as a separate 13 us phase afterwards.  (launch.h AsSide; the mixed launch below takes its second stream.)
+  static thread_local AsSide<2> side;
+  const bool serial = getenv("AS_SDPA_SERIAL") != nullptr;   // (read per call)
+  const bool concurrent = ns > 0 && qtiles > 0 && !serial && as_side_fork(side, s, 1);
+  hipStream_t s2 = concurrent ? side.cur->st[0] : s;
 #define AS_PIPE_LAUNCH_MIX(NQ_, SPLIT_, MODE_, GRID_, STREAM_, QT_, NS_, WS_, MIX_, MIXA_, MIXR_)                                                  \
   hipLaunchKernelGGL((sdpa_fwd_pipe_kernel<NQ_, SPLIT_, MODE_>), dim3(GRID_), dim3(SD_NT), lds, STREAM_, (const __bf16*)q,  \
                      (const __bf16*)k, (const __bf16*)vt, (__bf16*)o, lse, B, N, Npad, h, QT_, NS_, (float*)(WS_), MIX_, MIXA_, MIXR_)
@@ -1498,15 +1442,10 @@ int launch_sdpa_glds(const void* q, const void* k, const void* vt, void* o, floa
   if (mixed) {
     // three concurrent launches: 256-row workgroups on the caller's stream, 128-row workgroups and the key-split ragged
     // rows on two helper streams (fork / join with events), so the dispatcher can place one of each kind on every CU
-    static std::atomic<bool> attr_mix{false};
     const size_t lds2 = (size_t)AS_SDPA_NBUF2 * 2 * GL_TILE;
-    if (!attr_mix && lds2 > 64 * 1024 - 1) {
-      (void)hipFuncSetAttribute((const void*)sdpa_fwd_pipe_kernel<2, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-      attr_mix = true;
-    }
-    bool forked = side.ok && getenv("AS_SDPA_SERIAL") == nullptr && hipEventRecord(side.fork, s) == hipSuccess && hipStreamWaitEvent(side.st, side.fork, 0) == hipSuccess &&
-                  hipStreamWaitEvent(side.st2, side.fork, 0) == hipSuccess;
-    hipStream_t sa = forked ? side.st : s, sb = forked ? side.st2 : s;
+    as_lds_optin<sdpa_fwd_pipe_kernel<2, false, 1>>(lds2);
+    const bool forked = !serial && as_side_fork(side, s);
+    hipStream_t sa = forked ? side.cur->st[0] : s, sb = forked ? side.cur->st[1] : s;
     {
       const size_t lds = lds2;
       AS_PIPE_LAUNCH_MIX(2, false, 1, mix.X, s, 0, 1, nullptr, 1, mix.a, mix.r);
@@ -1524,20 +1463,14 @@ int launch_sdpa_glds(const void* q, const void* k, const void* vt, void* o, floa
       AS_CHECK_LAUNCH("sdpa_combine (mixed)");
     }
     if (forked) {
-      (void)hipEventRecord(side.join, side.st);
-      (void)hipEventRecord(side.join2, side.st2);
-      (void)hipStreamWaitEvent(s, side.join, 0);
-      (void)hipStreamWaitEvent(s, side.join2, 0);
+      as_side_join(side, 0, s);
+      as_side_join(side, 1, s);
     }
     return AS_OK;
   }
   if (impl == 7) {                                           // 512-row workgroups of 8 waves (64 queries per wave), one per CU
     const size_t lds = (size_t)AS_SDPA_NBUF2 * 2 * GL_TILE;
-    static std::atomic<bool> attr_w8{false};
-    if (!attr_w8 && lds > 64 * 1024 - 1) {
-      (void)hipFuncSetAttribute((const void*)sdpa_fwd_pipe_kernel<2, 0, 1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_w8 = true;
-    }
+    as_lds_optin<sdpa_fwd_pipe_kernel<2, 0, 1, 8>>(lds);
     hipLaunchKernelGGL((sdpa_fwd_pipe_kernel<2, 0, 1, 8>), dim3(as_ceil_div(N, 512) * BH), dim3(512), lds, s, (const __bf16*)q,
                        (const __bf16*)k, (const __bf16*)vt, (__bf16*)o, lse, B, N, Npad, h, 0, 1, (float*)nullptr, 0, 0, 0);
     AS_CHECK_LAUNCH("sdpa_fwd_pipe<8 waves>");
@@ -1545,11 +1478,7 @@ int launch_sdpa_glds(const void* q, const void* k, const void* vt, void* o, floa
   }
   if (impl == 6) {                                           // stream-K: persistent, balanced, merged in the kernel
     const size_t lds = (size_t)AS_SDPA_NBUF2 * 2 * GL_TILE;
-    static std::atomic<bool> attr_sk{false};
-    if (!attr_sk && lds > 64 * 1024 - 1) {
-      (void)hipFuncSetAttribute((const void*)sdpa_fwd_pipe_kernel<2, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_sk = true;
-    }
+    as_lds_optin<sdpa_fwd_pipe_kernel<2, 2, 1>>(lds);
     const char* dbg_e = getenv("AS_SDPA_SK_DEBUG");               // experiments: 1 identity ranks, 2 no exchange, 4 no memset
     const int dbg = dbg_e ? atoi(dbg_e) : 0;
     if (!(dbg & 4) && hipMemsetAsync(ws, 0, sdpa_sk_counter_bytes(B, N, h), s) != hipSuccess) {
@@ -1565,14 +1494,13 @@ int launch_sdpa_glds(const void* q, const void* k, const void* vt, void* o, floa
     const size_t lds1 = lds;
     const size_t lds = (size_t)AS_SDPA_NBUF2 * 2 * GL_TILE;
     (void)lds1;
-    static std::atomic<bool> attr_set{false};   // (idempotent attribute call: a race only repeats it)
-    if (!attr_set && lds > 64 * 1024 - 1) {
-      (void)hipFuncSetAttribute((const void*)sdpa_fwd_pipe_kernel<2, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute((const void*)sdpa_fwd_pipe_kernel<2, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
+    if (impl == 2) {
+      as_lds_optin<sdpa_fwd_pipe_kernel<2, false, 0>>(lds);
+      AS_PIPE_LAUNCH(2, false, 0, grid2, s, 0, 1, nullptr);
+    } else {
+      as_lds_optin<sdpa_fwd_pipe_kernel<2, false, 1>>(lds);
+      AS_PIPE_LAUNCH(2, false, 1, grid2, s, 0, 1, nullptr);
     }
-    if (impl == 2) AS_PIPE_LAUNCH(2, false, 0, grid2, s, 0, 1, nullptr);
-    else AS_PIPE_LAUNCH(2, false, 1, grid2, s, 0, 1, nullptr);
     AS_CHECK_LAUNCH("sdpa_fwd_pipe<2>");
     return AS_OK;
   }
@@ -1586,7 +1514,6 @@ int launch_sdpa_glds(const void* q, const void* k, const void* vt, void* o, floa
     hipLaunchKernelGGL(sdpa_combine_kernel, dim3(SD_QB / 16, BH), dim3(256), 0, s2, (const float*)ws, (__bf16*)o, lse, B, N,
                        h, qtiles, ns);
     AS_CHECK_LAUNCH("sdpa_combine");
-    if (s2 != s) (void)hipEventRecord(side.join, s2);
   }
   if (qtiles > 0) {
     if (impl == 1) AS_PIPE_LAUNCH(1, false, 0, qtiles * BH, s, 0, 1, nullptr);
@@ -1598,7 +1525,7 @@ int launch_sdpa_glds(const void* q, const void* k, const void* vt, void* o, floa
   }
 #undef AS_PIPE_LAUNCH
 #undef AS_PIPE_LAUNCH_MIX
-  if (ns > 0 && s2 != s) (void)hipStreamWaitEvent(s, side.join, 0);     // join: later work on `s` sees the split rows
+  if (concurrent) as_side_join(side, 0, s);                  // later work on `s` sees the split rows
   return AS_OK;
 }
 
@@ -1608,11 +1535,7 @@ int launch_sdpa(const void* q, const void* k, const void* vt, void* o, float* ls
   const int Npad = as_round_up(N, 64);
   const int grid = as_ceil_div(N, SD_QB) * B * h;
   const size_t lds = 2 * ((size_t)SD_KB * SdpaCfg<T>::K_PITCH + (size_t)HD * SdpaCfg<T>::V_PITCH);
-  static std::atomic<bool> attr_set{false};   // (idempotent attribute call: a race only repeats it)
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)sdpa_fwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  as_lds_optin<sdpa_fwd_kernel<T>>(lds);
   hipLaunchKernelGGL((sdpa_fwd_kernel<T>), dim3(grid), dim3(SD_NT), lds, s, (const T*)q, (const T*)k,
                      (const T*)vt, (T*)o, lse, B, N, Npad, h);
   AS_CHECK_LAUNCH("sdpa_fwd");

@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "lds_asm.h"
+#include "launch.h"
 
 namespace {
 
@@ -1386,42 +1387,30 @@ int launch_bwd(const void* q, const void* k, const void* vt, const void* o, cons
   constexpr int PITCH = TS::ROWB + 16;
   const size_t lds_dq = 2 * (size_t)(3 * BW_TILE * PITCH);
   const size_t lds_dkv = 2 * (size_t)(2 * BW_TILE * TS::ROWB + 2 * BW_TILE * PITCH + 2 * BW_TILE * 4);
-  static std::atomic<bool> attr_set{false};   // (idempotent attribute call: a race only repeats it)
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)sdpa_bwd_dq_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dq);
-    (void)hipFuncSetAttribute((const void*)sdpa_bwd_dkv_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dkv);
-    attr_set = true;
-  }
+  as_lds_optin<sdpa_bwd_dq_kernel<T>>(lds_dq);           // (the fp32 / AS_BWD_OLD pair at the end of this function)
+  as_lds_optin<sdpa_bwd_dkv_kernel<T>>(lds_dkv);
   const int tiles = as_ceil_div(N, 128);
   static const bool old_dkv = getenv("AS_BWD_OLD") != nullptr;       // (experiments: the register-staged kernel)
   // dQ depends on the prep kernel only and writes its own third of dqkv: the bf16 kernels run it CONCURRENTLY with dK/dV
-  // on a helper stream (fork after prep, join on the caller's stream).  (common.h AsSide.)
-  static thread_local AsSide side;
-  hipStream_t sq = s;
-  if (sizeof(T) == 2 && !old_dkv) sq = as_side_fork(side, s);
+  // on a helper stream (fork after prep, join on the caller's stream; launch.h AsSide).  AS_BWD_SERIAL=1 keeps everything
+  // on the caller's stream.
+  static thread_local AsSide<1> side;
+  static const bool serial = getenv("AS_BWD_SERIAL") != nullptr;
+  const bool forked = sizeof(T) == 2 && !old_dkv && !serial && as_side_fork(side, s);
+  hipStream_t sq = forked ? side.cur->st[0] : s;
   if constexpr (sizeof(T) == 2) {
     if (!old_dkv) {
       const size_t lds_dkv_dma = (size_t)AS_BWD_NST * DK_STAGE, lds_dq_dma = 2 * (size_t)DQ_STAGE;
       auto go_dkv = [&](auto nk_c, auto nw_c) {
         constexpr int NK = decltype(nk_c)::value, NW = decltype(nw_c)::value;
-        static std::atomic<bool> attr{false};
-        if (!attr) {
-          (void)hipFuncSetAttribute((const void*)sdpa_bwd_dkv_dma_kernel<NK, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_dkv_dma);
-          attr = true;
-        }
+        as_lds_optin<sdpa_bwd_dkv_dma_kernel<NK, NW>>(lds_dkv_dma);
         hipLaunchKernelGGL((sdpa_bwd_dkv_dma_kernel<NK, NW>), dim3(BH * as_ceil_div(N, 32 * NK * NW)), dim3(64 * NW), lds_dkv_dma, s,
                            (const __bf16*)q, (const __bf16*)dof, (const __bf16*)qt, (const __bf16*)dot, (const __bf16*)k,
                            (const __bf16*)vrow, (const float*)lse2, (const float*)delta, (__bf16*)dqkv, B, N, Npad, h);
       };
       auto go_dq = [&](auto nq_c, auto nw_c) {
         constexpr int NQ = decltype(nq_c)::value, NW = decltype(nw_c)::value;
-        static std::atomic<bool> attr{false};
-        if (!attr) {
-          (void)hipFuncSetAttribute((const void*)sdpa_bwd_dq_dma_kernel<NQ, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_dq_dma);
-          attr = true;
-        }
+        as_lds_optin<sdpa_bwd_dq_dma_kernel<NQ, NW>>(lds_dq_dma);
         hipLaunchKernelGGL((sdpa_bwd_dq_dma_kernel<NQ, NW>), dim3(BH * as_ceil_div(N, 32 * NQ * NW)), dim3(64 * NW), lds_dq_dma, sq,
                            (const __bf16*)q, (const __bf16*)dof, (const __bf16*)k, (const __bf16*)vrow, (const __bf16*)kt, lse,
                            (const float*)delta, (__bf16*)dqkv, B, N, Npad, h);
@@ -1429,12 +1418,8 @@ int launch_bwd(const void* q, const void* k, const void* vt, const void* o, cons
       if (use_tr && !prep_scalar) {
         constexpr int NSTK = AS_BWD_TR_NST_DKV, NSTQ = AS_BWD_TR_NST_DQ;
         const size_t lds_k = (size_t)NSTK * T3_DKV_STAGE, lds_q = (size_t)NSTQ * T3_DQ_STAGE;
-        static std::atomic<bool> attr{false};
-        if (!attr) {
-          (void)hipFuncSetAttribute((const void*)sdpa_bwd_dkv_tr_kernel<NSTK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_k);
-          (void)hipFuncSetAttribute((const void*)sdpa_bwd_dq_tr_kernel<NSTQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);
-          attr = true;
-        }
+        as_lds_optin<sdpa_bwd_dkv_tr_kernel<NSTK>>(lds_k);
+        as_lds_optin<sdpa_bwd_dq_tr_kernel<NSTQ>>(lds_q);
         // (workspace slots under ROWM: dof = dO rows, qt = q rows, kt = k rows)
         static const int only = getenv("AS_BWD_ONLY") ? atoi(getenv("AS_BWD_ONLY")) : 0;      // (timing experiments: 1 dK/dV, 2 dQ, 3 the prep kernel alone)
         if (only != 2 && only != 3)
@@ -1445,7 +1430,7 @@ int launch_bwd(const void* q, const void* k, const void* vt, const void* o, cons
         hipLaunchKernelGGL((sdpa_bwd_dq_tr_kernel<NSTQ>), dim3(BH * tiles), dim3(BW_NT), lds_q, sq, (const __bf16*)qt, (const __bf16*)dof,
                            (const __bf16*)kt, (const __bf16*)vrow, lse, (const float*)delta, (__bf16*)dqkv, B, N, Npad, h);
         AS_CHECK_LAUNCH("sdpa_bwd_dq_tr");
-        as_side_join(side, sq, s);
+        if (forked) as_side_join(side, 0, s);
         return AS_OK;
       }
       // (round 4 tried other workgroup shapes of these two kernels -- 8 waves sharing a staged tile, 64 rows per wave:
@@ -1454,7 +1439,7 @@ int launch_bwd(const void* q, const void* k, const void* vt, const void* o, cons
       go_dkv(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
       AS_CHECK_LAUNCH("sdpa_bwd_dkv");
       go_dq(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
-      as_side_join(side, sq, s);                          // the caller's stream continues after dQ as well
+      if (forked) as_side_join(side, 0, s);               // the caller's stream continues after dQ as well
     }
   }
   if (sizeof(T) != 2 || old_dkv)
