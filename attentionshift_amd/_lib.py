@@ -110,6 +110,9 @@ SIGNATURES = {
     "as_rpn_candidates_workspace_bytes": (_c_size_t, [_c_int] * 2),
     "as_rpn_candidates": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p] * 2 + [_c_int, _c_float, _c_void_p, _c_float, _c_int]
                           + [_c_void_p] * 7 + [_c_size_t, _c_void_p]),
+    "as_det_candidates_workspace_bytes": (_c_size_t, [_c_int] * 2),
+    "as_det_candidates": (_c_int, [_c_void_p] * 2 + [_c_int, _c_void_p] + [_c_int] * 3 + [_c_float] + [_c_void_p] * 3 + [_c_float]
+                          + [_c_void_p] * 8 + [_c_size_t, _c_void_p]),
     "as_rpn_assign_workspace_bytes": (_c_size_t, [_c_int] * 3),
     "as_rpn_assign": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p] * 3 + [_c_int] * 2 + [_c_void_p] + [_c_float] * 3
                       + [_c_int] * 2 + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),

@@ -15,6 +15,8 @@ csrc/detect_post.hip (ops.nms / ops.paste_masks), unless AS_POST_HOST=1 forces t
     rpn_candidates /       mmdet/models/dense_heads/rpn_head.py:82-236 (RPNHead._get_bboxes): per-level top nms_pre by
     rpn_nms /              logit, anchors (anchor_generator.py:142-270), delta2bbox, minimum size, then mmcv's batched_nms
     rpn_proposals          with the level as the class; device tensors run csrc/rpn.hip (ops.rpn_candidates) and as_nms
+    det_candidates         get_det_bboxes up to the NMS as select / order / decode-the-survivors; device tensors run
+                           csrc/det.hip (ops.det_candidates).  Opt-in: get_det_bboxes(fused=True), test_cfg.fused_det
 """
 import os
 
@@ -165,9 +167,96 @@ def rpn_proposals(cls_scores, bbox_preds, base_anchors, strides, img_shapes, nms
     return [rpn_nms(box[b, :m], nms_box[b, :m], score[b, :m], iou_threshold, max_per_img)[0] for b, m in enumerate(counts)]
 
 
+def _final_boxes(rois, img_shape):
+    """bbox_pred is None: the RoIs clamped to the image are the boxes (the tensor ops of BBoxHead.get_bboxes)"""
+    bboxes = rois[:, 1:].clone()
+    bboxes[:, 0::2] = bboxes[:, 0::2].clamp(0, img_shape[1])
+    bboxes[:, 1::2] = bboxes[:, 1::2].clamp(0, img_shape[0])
+    return bboxes
+
+
+def _det_candidates_host(boxes_or_rois, bbox_pred, scores, img_shape, scale, score_thr, means, stds, apply_softmax=True,
+                         return_prob=False):
+    """The definition of det_candidates in the tensor ops of get_det_bboxes / multiclass_nms (any device).  boxes_or_rois:
+    the RoIs [n,4] with bbox_pred, else final boxes [n,4] / [n,4K]; scale: 4 divisors or None."""
+    n, K = scores.shape[0], scores.shape[1] - 1
+    dev = scores.device
+    prob = F.softmax(scores, dim=-1) if apply_softmax else scores
+    if bbox_pred is not None:
+        bboxes = delta2bbox(boxes_or_rois, bbox_pred, means, stds, max_shape=img_shape)
+    else:
+        bboxes = boxes_or_rois
+    if scale is not None and bboxes.size(0) > 0:
+        sf = bboxes.new_tensor(scale)
+        bboxes = (bboxes.view(bboxes.size(0), bboxes.shape[1] // 4, 4) / sf).view(bboxes.size(0), -1)
+    cap = min(n * K, ops.DET_MAX_CANDIDATES)
+    out_box, out_nms = prob.new_zeros(cap, 4), prob.new_zeros(cap, 4)
+    out_score = prob.new_zeros(cap)
+    out_roi = torch.zeros(cap, dtype=torch.int32, device=dev)
+    out_label = torch.zeros(cap, dtype=torch.int32, device=dev)
+    if bboxes.shape[1] > 4:
+        bboxes = bboxes.view(n, bboxes.shape[1] // 4, 4)
+    else:
+        bboxes = bboxes[:, None].expand(n, K, 4)
+    sc = prob[:, :-1]
+    labels = torch.arange(K, dtype=torch.long, device=dev).view(1, -1).expand_as(sc)
+    rows = torch.arange(n, dtype=torch.long, device=dev).view(-1, 1).expand_as(sc)
+    valid = sc > score_thr
+    bboxes, sc, labels, rows = bboxes[valid], sc[valid], labels[valid], rows[valid]
+    m = int(sc.numel())
+    if 0 < m <= cap:
+        offsets = labels.to(bboxes) * (bboxes.max() + 1)
+        order = sc.argsort(descending=True, stable=True)
+        out_box[:m], out_score[:m] = bboxes[order], sc[order]
+        out_nms[:m] = (bboxes + offsets[:, None])[order]
+        out_roi[:m], out_label[:m] = rows[order].to(torch.int32), labels[order].to(torch.int32)
+    out = (out_box, out_nms, out_score, out_roi, out_label, torch.tensor([m], dtype=torch.int32, device=dev))
+    return out + (prob,) if return_prob else out
+
+
+def det_candidates(rois, cls_score, bbox_pred, img_shape, scale_factor, rescale, score_thr=0.05, means=(0., 0., 0., 0.),
+                   stds=(0.1, 0.1, 0.2, 0.2), apply_softmax=True, return_prob=False):
+    """The box head's test-time stage before NMS for ONE image: BBoxHead.get_bboxes and the front of multiclass_nms
+    (mmdet/core/post_processing/bbox_nms.py:34-93) as select, order, decode only the survivors.  rois [n,5] (batch index
+    first), cls_score [n,K+1] (the last column is the background), bbox_pred [n,4] / [n,4K] or None.
+      Scores: p = cls_score, or with apply_softmax p[r,c] = exp(x[r,c] - max x[r,:]) / sum exp(x[r,:] - max) over the K + 1
+        columns in fp32; a row holding NaN or +inf has NaN probabilities and no candidate.
+      Candidates: all (r, c), c < K, with p[r,c] > fp32(score_thr), compared in fp32; a NaN never qualifies.
+      Order: score descending, then the flat index r * K + c ascending; -0.0 == +0.0 (a stable descending argsort).
+      Box of (r, c): delta2bbox of RoI r with the deltas of column block c (block 0 for [n,4] deltas): means, stds, dw / dh
+        clamped to +-|log(16/1000)|, clipped to img_shape; bbox_pred None: the RoI clamped to the image.  With rescale each
+        coordinate j is then divided by scale_factor[j] (a scalar factor divides all four).
+    -> (cand_box [cap,4], cand_nms_box [cap,4], cand_score [cap], cand_roi [cap] int32, cand_label [cap] int32,
+        cand_count [1] int32[, prob [n,K+1]]), cap = min(n * K, 65535), the first m = cand_count rows in that order;
+    cand_nms_box = cand_box + label * (M + 1) in fp32, M the largest coordinate of all candidate boxes (batched_nms' class
+    offset: the input of NMS).  With m > 65535 only the count is meaningful.  Device tensors run csrc/det.hip
+    (ops.det_candidates: every step but exp rounds as the tensor ops, nothing is read back) unless AS_POST_HOST=1; CPU
+    tensors the tensor ops of get_det_bboxes / multiclass_nms themselves."""
+    cls_score = cls_score.float().contiguous()
+    scale = None
+    if rescale:
+        scale = [float(v) for v in np.broadcast_to(np.asarray(scale_factor, dtype=np.float32).reshape(-1), (4,))]
+    deltas = bbox_pred.float().contiguous() if bbox_pred is not None else None
+    boxes = rois[:, 1:].float().contiguous() if bbox_pred is not None else _final_boxes(rois.float(), img_shape).contiguous()
+    if _on_device(cls_score):
+        return ops.det_candidates(boxes, deltas, cls_score, score_thr, img_shape, scale, means, stds, apply_softmax, return_prob)
+    return _det_candidates_host(boxes, deltas, cls_score, img_shape, scale, score_thr, means, stds, apply_softmax, return_prob)
+
+
 def get_det_bboxes(rois, cls_score, bbox_pred, img_shape, scale_factor, rescale, score_thr=0.05, iou_threshold=0.5,
-                   max_per_img=100, means=(0., 0., 0., 0.), stds=(0.1, 0.1, 0.2, 0.2)):
-    """rois [n,5] (batch index first) of ONE image -> (det_bboxes [m,5], det_labels [m])."""
+                   max_per_img=100, means=(0., 0., 0., 0.), stds=(0.1, 0.1, 0.2, 0.2), fused=False):
+    """rois [n,5] (batch index first) of ONE image -> (det_bboxes [m,5], det_labels [m]).  fused: det_candidates (one call of
+    csrc/det.hip on device tensors), one readback of the count, NMS over the class-offset candidates in their order."""
+    if fused:
+        box, nms_box, score, _, label, count = det_candidates(rois, cls_score, bbox_pred, img_shape, scale_factor, rescale,
+                                                              score_thr, means, stds)
+        m = int(count.item())
+        if m > ops.DET_MAX_CANDIDATES:
+            raise ops.AttnShiftError(f"get_det_bboxes: {m} candidates above score_thr, NMS takes at most {ops.DET_MAX_CANDIDATES}")
+        keep = _nms_in_order(nms_box[:m], iou_threshold, max_per_img)
+        if max_per_img > 0:
+            keep = keep[:max_per_img]
+        return torch.cat((box[keep], score[keep, None]), dim=1), label[keep].long()
     scores = F.softmax(cls_score, dim=-1) if cls_score is not None else None
     if bbox_pred is not None:
         bboxes = delta2bbox(rois[:, 1:], bbox_pred, means, stds, max_shape=img_shape)

@@ -1258,6 +1258,55 @@ def rpn_candidates(cls_scores, bbox_preds, base_anchors, strides, img_shapes, nm
 
 
 # ------------------------------------------------------------------------------------------------
+# Part C: the box head's detection candidates (csrc/det.hip)
+# ------------------------------------------------------------------------------------------------
+DET_MAX_CANDIDATES = 65535
+
+
+def det_candidates(rois_or_boxes, deltas, scores, score_thr, img_shape=None, scale=None, means=(0., 0., 0., 0.),
+                   stds=(0.1, 0.1, 0.2, 0.2), apply_softmax=True, return_prob=False, wh_ratio_clip=16 / 1000):
+    """One image's candidates for the class-aware NMS (as_det_candidates; the definition is inference.det_candidates').
+    scores [n,K+1] fp32 on the device (logits with apply_softmax); deltas [n,4] or [n,4K] with rois_or_boxes = the RoIs
+    [n,4], or deltas None and rois_or_boxes [n,4] / [n,4K] final boxes (no decode, no clip).  img_shape (h, w[, c]) or
+    None: no clip; scale: 4 divisors or None -> (cand_box [cap,4], cand_nms_box [cap,4], cand_score [cap], cand_roi [cap]
+    int32, cand_label [cap] int32, cand_count [1] int32[, prob [n,K+1]]), cap = min(n * K, 65535); the first cand_count rows
+    are written.  Nothing is read back."""
+    lib = _lib.load()
+    _chk(rois_or_boxes, deltas, scores, dtype=torch.float32)
+    if scores.dim() != 2 or scores.shape[1] < 2:
+        raise AttnShiftError(f"det_candidates: scores must be [n, K+1] with K >= 1, got {tuple(scores.shape)}")
+    n, K = int(scores.shape[0]), int(scores.shape[1]) - 1
+    coords = deltas if deltas is not None else rois_or_boxes
+    if coords.dim() != 2 or coords.shape[0] != n or coords.shape[1] not in (4, 4 * K):
+        raise AttnShiftError(f"det_candidates: boxes / deltas must be [{n}, 4] or [{n}, {4 * K}], got {tuple(coords.shape)}")
+    if deltas is not None and tuple(rois_or_boxes.shape) != (n, 4):
+        raise AttnShiftError(f"det_candidates: rois must be [{n}, 4], got {tuple(rois_or_boxes.shape)}")
+    Kb = int(coords.shape[1]) // 4
+    dev = scores.device
+    cap = min(n * K, DET_MAX_CANDIDATES)
+    cand_box = torch.empty(cap, 4, device=dev, dtype=torch.float32)
+    cand_nms_box = torch.empty(cap, 4, device=dev, dtype=torch.float32)
+    cand_score = torch.empty(cap, device=dev, dtype=torch.float32)
+    cand_roi = torch.empty(cap, device=dev, dtype=torch.int32)
+    cand_label = torch.empty(cap, device=dev, dtype=torch.int32)
+    cand_count = torch.empty(1, device=dev, dtype=torch.int32)
+    prob = torch.empty(n, K + 1, device=dev, dtype=torch.float32) if return_prob else None
+    shape = (ctypes.c_float * 2)(float(img_shape[0]), float(img_shape[1])) if img_shape is not None else None
+    sc = (ctypes.c_float * 4)(*[float(v) for v in scale]) if scale is not None else None
+    ms = (ctypes.c_float * 8)(*[float(v) for v in means], *[float(v) for v in stds])
+    nbytes = lib.as_det_candidates_workspace_bytes(n, K)
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    _lib.check(lib.as_det_candidates(_p(rois_or_boxes), _p(deltas), Kb, _p(scores), int(bool(apply_softmax)), n, K, float(score_thr),
+                                     ctypes.addressof(shape) if shape is not None else None,
+                                     ctypes.addressof(sc) if sc is not None else None, ctypes.addressof(ms),
+                                     abs(float(np.log(wh_ratio_clip))), _p(prob), _p(cand_box), _p(cand_nms_box), _p(cand_score),
+                                     _p(cand_roi), _p(cand_label), _p(cand_count), _p(ws), nbytes, _stream()),
+               "as_det_candidates")
+    out = (cand_box, cand_nms_box, cand_score, cand_roi, cand_label, cand_count)
+    return out + (prob,) if return_prob else out
+
+
+# ------------------------------------------------------------------------------------------------
 # RPN training targets (csrc/rpn_train.hip)
 # ------------------------------------------------------------------------------------------------
 def _rpn_grid_levels(featmap_sizes, strides):

@@ -994,7 +994,8 @@ class AttnShiftRoIHead(nn.Module):
                 cls_score, bbox_pred = props.new_zeros(0, bh.num_classes + 1), props.new_zeros(0, 4 * bh.num_classes)
             dets, labels = I.get_det_bboxes(rois, cls_score, bbox_pred, meta["img_shape"], meta.get("scale_factor", 1.0),
                                             rescale, _get(cfg, "score_thr", 0.05), nms_cfg.get("iou_threshold", 0.5),
-                                            _get(cfg, "max_per_img", 100), bh.target_means, bh.target_stds)
+                                            _get(cfg, "max_per_img", 100), bh.target_means, bh.target_stds,
+                                            fused=bool(_get(cfg, "fused_det", False)))
             boxes_res = I.bbox2result(dets, labels, bh.num_classes)
             if self.mask_head is None:
                 out.append(boxes_res)

@@ -500,7 +500,7 @@ int as_chamfer_2d_bwd(const float* xyz1, const float* xyz2, const float* gdist1,
                       const int32_t* idx2, float* gxyz1, float* gxyz2, int B, int n, int m, as_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Part C -- test-time post-processing of the RoI head (csrc/detect_post.hip, csrc/rle.hip)
+ * Part C -- test-time post-processing of the RoI head (csrc/detect_post.hip, csrc/rle.hip, csrc/rpn.hip, csrc/det.hip)
  * ------------------------------------------------------------------------------------------- */
 
 /* Greedy NMS, the mmcv.ops.nms behind mmdet/core/post_processing/bbox_nms.py:84 (batched_nms; IoU without the +1 offset):
@@ -589,6 +589,43 @@ int as_rpn_candidates(const as_rpn_level* levels, int L, int B, int A, const flo
                       int nms_pre, float min_bbox_size, const float* means_stds, float max_ratio, int C, float* cand_box,
                       float* cand_nms_box, float* cand_score, int32_t* cand_level, int32_t* cand_index, int32_t* cand_count,
                       void* workspace, size_t workspace_bytes, as_stream_t stream);
+
+/* The box head's detection candidates (csrc/det.hip): everything between the box head's outputs and the NMS of ONE image --
+ * BBoxHead.get_bboxes (mmdet/models/roi_heads/bbox_heads/bbox_head.py: softmax, decode, rescale), the decode of
+ * mmdet/core/bbox/coder/delta_xywh_bbox_coder.py:134-237, the threshold, gathers and ordering of multiclass_nms
+ * (mmdet/core/post_processing/bbox_nms.py:34-93) and the class offset of mmcv.ops.batched_nms -- in five launches without
+ * a host sync, decoding only the boxes that pass the threshold.
+ *   scores [n,K+1] fp32, the last column the background class (never a candidate); deltas [n,4*Kb] fp32 with Kb = 1 (one
+ *   shared / class-agnostic box per RoI) or K, and then rois_or_boxes = the RoIs [n,4]; deltas == NULL: rois_or_boxes
+ *   [n,4*Kb] are final boxes, taken as they are (no decode, no clip; the scale still applies).  img_shape (h, w), scale
+ *   (4 divisors) and means_stds (the 4 means, then the 4 stds) are HOST arrays; img_shape NULL: no clip, scale NULL: no
+ *   rescale, means_stds may be NULL without deltas.  max_ratio = |log(wh_ratio_clip)|.
+ * Scores: p = scores, or with apply_softmax p[r,c] = exp(x[r,c] - max_c' x[r,c']) / sum_c' exp(x[r,c'] - max) over the K + 1
+ *   columns in fp32 (a correctly rounded divide; the sum in no fixed association).  A row that holds a NaN or +inf has NaN
+ *   probabilities, as torch.softmax gives, and so no candidate.  prob_out [n,K+1], when not NULL, receives p.
+ * Candidates: all (r, c), c < K, with p[r,c] > score_thr, compared in fp32 (the caller's threshold rounded to fp32, as the
+ *   tensor op compares); a NaN never qualifies.  m = their number.
+ * Order: score descending, then the flat index r * K + c ascending; -0.0 == +0.0 (a stable descending argsort).
+ * Box of (r, c): delta2bbox of RoI r with the deltas of column block c (block 0 when Kb == 1): d = delta * std + mean, dw / dh
+ *   clamped to +-max_ratio, (gx, gy) = centre + size * (dx, dy), (gw, gh) = size * exp(dw, dh), corners gx -+ gw / 2, clipped
+ *   to [0, w] x [0, h]; every step but exp rounds as the ATen ops of the tensor-op route do (no contraction).  Then each
+ *   coordinate j is divided by scale[j], correctly rounded.
+ * Outputs, rows 0 .. m-1 in that order (rows past m are not written), cap = min(n * K, 65535) rows each:
+ *   cand_box [cap,4] fp32, cand_score [cap] fp32 (the bits of p), cand_roi [cap] int32 (r), cand_label [cap] int32 (c),
+ *   cand_nms_box [cap,4] fp32 = cand_box + (float)label * (M + 1), M the largest coordinate of all candidate boxes (NaN
+ *   propagating, as Tensor.max()), the fp32 operations in that order: as_nms' input.  cand_count [1] int32 = m.
+ *   When m > 65535 (as_nms' limit) only cand_count is meaningful.
+ * Limits: n <= 65535, K <= 255, n * K <= 2^20; beyond them AS_E_UNSUPPORTED.  n < 0, K < 1 and Kb outside {1, K} are
+ *   AS_E_BADARG.  n == 0 writes cand_count = 0 (when not NULL) and launches nothing else.
+ * Workspace: as_det_candidates_workspace_bytes(n, K) = 16 * ceil(cap / 2) + 16 * ceil((n + 1) / 4) + 16 * ceil(n * (K + 1) / 4)
+ *   bytes (the keys, the rows' offsets, the probabilities; 0 when n or K <= 0), 16-byte aligned like rois_or_boxes, cand_box
+ *   and cand_nms_box. */
+size_t as_det_candidates_workspace_bytes(int n, int K);
+int as_det_candidates(const float* rois_or_boxes, const float* deltas, int Kb, const float* scores, int apply_softmax, int n,
+                      int K, float score_thr, const float* img_shape, const float* scale, const float* means_stds,
+                      float max_ratio, float* prob_out, float* cand_box, float* cand_nms_box, float* cand_score,
+                      int32_t* cand_roi, int32_t* cand_label, int32_t* cand_count, void* workspace, size_t workspace_bytes,
+                      as_stream_t stream);
 
 /* RPN training targets (csrc/rpn_train.hip): what AnchorHead._get_targets_single (mmdet/models/dense_heads/anchor_head.py:
  * 175-271) does per image before the losses, for all B images and L levels, without an anchor tensor or an IoU matrix.

@@ -5,6 +5,9 @@
     ... to COCO RLE  the same masks as run-length strings: get_seg_masks(encode_rle=True), encoded on the device
                      (csrc/rle.hip), against the bitmap get_seg_masks + encode_mask_results on the host; and the
                      encode kernels alone
+    get_det_bboxes   the stage from the box head's outputs to the detections (softmax, decode, rescale, threshold, order, NMS) at
+                     1000 x 20, 1000 x 80 and 300 x 20: the fused candidates of csrc/det.hip (fused=True) against the tensor ops
+                     of the default route, both followed by as_nms; HIP events around each call, the count readbacks included
     rpn_proposals    one image's five levels at 1024 x 1024 (261 888 anchors), nms_pre 1000, max_per_img 1000, IoU 0.7 (the
                      shipped test_cfg.rpn): csrc/rpn.hip + as_nms against the tensor-op route, and the stage before NMS alone
 
@@ -94,9 +97,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--legs", default="all", choices=["all", "det"], help="det: only the get_det_bboxes leg")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     torch.set_grad_enabled(False)
+    if args.legs == "det":
+        text = "\n".join(det_leg(args)[1:]) + "\n"
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text)
+        return
     gen = torch.Generator().manual_seed(2)
     n, K = 1000, 20
     xy = torch.rand(n, 2, generator=gen) * 900
@@ -183,7 +194,7 @@ def main():
         "(the 105 MB fit the Infinity Cache).  "
         f"{runs} value changes in all; {copied} bytes are copied to the host ({rle_bytes} bytes of strings) instead of {m * H * W}.",
         "The device and the host encoding return identical strings.",
-    ] + rpn_lines
+    ] + rpn_lines + det_leg(args)
     text = "\n".join(lines) + "\n"
     print(text)
     if args.out:
@@ -256,6 +267,96 @@ def rpn_leg(args, gen):
         f"The two routes select the same candidates in the same order: {order_equal}; their proposals agree within rtol 1e-6 / atol 1e-5 "
         f"(they differ in `exp` alone): {same}.",
     ]
+
+
+def _count_syncs(fn):
+    """-> host synchronizations torch makes in one call of fn (its sync debug mode warns at each)"""
+    import warnings
+    torch.cuda.set_sync_debug_mode("warn")
+    try:
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            fn()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    return sum("synchroniz" in str(x.message) for x in w)
+
+
+def _count_launches(fn):
+    """-> kernel launches in one call of fn as torch's profiler traces them (copies and memsets left out); None when the
+    profiler gives no device activity"""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        names = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA")]
+        n = sum(1 for x in names if "memcpy" not in x.lower() and "memset" not in x.lower())
+        return n or None
+    except Exception:
+        return None
+
+
+def det_leg(args):
+    """get_det_bboxes of one image: the default route on device tensors (tensor ops, then as_nms) against fused=True
+    (as_det_candidates, one count readback, as_nms).  HIP events around every call, the routes alternating call by call."""
+    lines = [
+        "",
+        "## The box head's detection stage (`csrc/det.hip` + `as_nms`)",
+        "",
+        f"`python tools/post_bench.py --legs det --repeats {args.repeats} --warmup {args.warmup}` on {torch.cuda.get_device_name(0)}.  "
+        "`get_det_bboxes` of one image from the box head's outputs to the detections: logits `[n, K+1]`, per-class deltas "
+        "`[n, 4K]`, a 1024 x 1024 image, rescale by four factors, `score_thr` 0.05, IoU 0.5, 100 kept.  Time between HIP events "
+        "around each call, the count readbacks included, median (min) in ms; the two routes alternate call by call.  Launches are "
+        "what torch's profiler traces in one call (copies and memsets left out), syncs what its sync debug mode reports.",
+        "",
+        "| n x K | candidates | tensor ops + `as_nms` (default) | launches | syncs | fused (`fused_det`) | launches | syncs | default / fused |",
+        "|---|---|---|---|---|---|---|---|---|",
+    ]
+    notes, alone = [], []
+    for n, K in ((1000, 20), (1000, 80), (300, 20)):
+        gen = torch.Generator().manual_seed(100 * n + K)
+        xy = torch.rand(n, 2, generator=gen) * 900
+        rois = torch.cat((torch.zeros(n, 1), xy, xy + 10 + torch.rand(n, 2, generator=gen) * 200), 1).cuda()
+        logits = (torch.randn(n, K + 1, generator=gen) * 2.5).cuda()
+        pred = (torch.randn(n, 4 * K, generator=gen) * 0.5).cuda()
+        sf = np.array([1.25, 1.5, 1.25, 1.5], dtype=np.float32)
+        call = {r: (lambda f=(r == "fused"): I.get_det_bboxes(rois, logits, pred, (1024, 1024, 3), sf, True, 0.05, 0.5, 100, fused=f))
+                for r in ("default", "fused")}
+        ts, out = {"default": [], "fused": []}, {}
+        for r in range(args.warmup + args.repeats):
+            for route in ("default", "fused"):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out[route] = call[route]()
+                e1.record()
+                torch.cuda.synchronize()
+                if r >= args.warmup:
+                    ts[route].append(e0.elapsed_time(e1))
+        med = {k: statistics.median(v) for k, v in ts.items()}
+        cand = int(I.det_candidates(rois, logits, pred, (1024, 1024, 3), sf, True, 0.05)[5])
+        # the five kernels of as_det_candidates by themselves: HIP events around back-to-back calls (allocations included)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.repeats):
+            I.det_candidates(rois, logits, pred, (1024, 1024, 3), sf, True, 0.05)
+        e1.record()
+        torch.cuda.synchronize()
+        alone.append(f"{n} x {K}: {e0.elapsed_time(e1) / args.repeats:.3f} ms")
+        syncs = {k: _count_syncs(call[k]) for k in call}
+        launches = {k: _count_launches(call[k]) for k in call}
+        (dd, ld), (df, lf) = out["default"], out["fused"]
+        same = dd.shape == df.shape and torch.equal(ld, lf) and torch.allclose(dd, df, rtol=1e-5, atol=1e-4)
+        notes.append(f"{n} x {K}: {dd.shape[0]} / {df.shape[0]} detections, the same labels and boxes within rtol 1e-5 / atol 1e-4: {same}")
+        fmt = lambda v: "not measured" if v is None else str(v)      # noqa: E731
+        lines.append(f"| {n} x {K} | {cand} | {med['default']:.3f} ({min(ts['default']):.3f}) | {fmt(launches['default'])} | "
+                     f"{syncs['default']} | {med['fused']:.3f} ({min(ts['fused']):.3f}) | {fmt(launches['fused'])} | {syncs['fused']} | "
+                     f"{med['default'] / med['fused']:.2f} |")
+    lines += ["", "The two routes' detections (default / fused): " + "; ".join(notes) + ".",
+              "The fused route's launches are the five of `as_det_candidates`, the two of `as_nms` and torch's gather of the kept rows.",
+              f"`det_candidates` alone (five launches, no readback) between HIP events over {args.repeats} back-to-back calls: "
+              + "; ".join(alone) + "."]
+    return lines
 
 
 def _host_paste(logits, labels, dets, H, W):
