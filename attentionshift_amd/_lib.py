@@ -25,6 +25,8 @@ SIGNATURES = {
     "as_linear_gelu_fwd": (_c_int, [_c_void_p] * 5 + [_c_int] * 4 + [_c_void_p]),
     "as_linear_dgelu_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 4 + [_c_void_p]),
     "as_deconv2x2_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 6 + [_c_void_p]),
+    "as_conv2d_tile_n": (_c_int, [_c_int]),
+    "as_conv2d_fwd": (_c_int, [_c_void_p, ctypes.c_longlong] + [_c_void_p] * 3 + [_c_int] * 10 + [_c_void_p] * 2),
     "as_qkv_fwd": (_c_int, [_c_void_p] * 6 + [_c_int] * 5 + [_c_void_p]),
     "as_sdpa_fwd_workspace_bytes": (_c_size_t, [_c_int] * 4),
     "as_sdpa_fwd": (_c_int, [_c_void_p] * 6 + [_c_size_t] + [_c_int] * 4 + [_c_void_p]),

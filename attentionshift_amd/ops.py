@@ -272,6 +272,60 @@ def deconv2x2(x_nhwc, w4, bias4=None, act="none"):
     return out
 
 
+def pack_conv_weight(weight_oihw, pad_to=16):
+    """Conv2d weight [Cout, Cin, k, k] -> the bf16 tap-major [Cout', k, k, Cin] as_conv2d_fwd reads (a tap's Cin run is
+    contiguous); Cout' = Cout rounded up to `pad_to` rows of zeros (the kernel's contract: Cout % 16 == 0)."""
+    w = weight_oihw.detach().permute(0, 2, 3, 1).to(torch.bfloat16)
+    extra = -w.shape[0] % int(pad_to)
+    if extra:
+        w = torch.cat([w, w.new_zeros((extra,) + tuple(w.shape[1:]))])
+    return w.contiguous()
+
+
+def conv2d_tile_n(cout):
+    """output channels per tile of the variant as_conv2d_fwd's launcher takes for `cout` (128 or 32; a host function)"""
+    return _lib.load().as_conv2d_tile_n(int(cout))
+
+
+def conv2d_nhwc(x, w_packed, bias=None, ksize=3, act="none", add=None, out_dtype=None):
+    """Stride-1 convolution with padding (ksize - 1) / 2 of a channels-last bf16 map (csrc/conv.hip as_conv2d_fwd).
+    x [B,H,W,Cin] bf16: every image dense ([H,W,Cin] contiguous), the images may be strided (a view into a token tensor is
+    read in place); w_packed [Cout,ksize,ksize,Cin] bf16 (pack_conv_weight); bias fp32 [Cout] | None; add bf16
+    [B,Ha,Wa,Cout] | None: out += add[b, sy(y), sx(x)] with ATen's nearest source index (the FPN's top-down path);
+    act "none" | "relu"; out_dtype bf16 (default) | fp32.  -> [B,H,W,Cout].  fp32 accumulator + bias + add, act, one rounding."""
+    lib = _lib.load()
+    if not (x.is_cuda and w_packed.is_cuda):
+        raise AttnShiftError("hot-path ops need device (HBM) tensors; there is no CPU fallback")
+    if x.dim() != 4 or w_packed.dim() != 4:
+        raise AttnShiftError("conv2d_nhwc: x [B,H,W,Cin] and w_packed [Cout,k,k,Cin] expected")
+    B, H, W, Cin = x.shape
+    Cout = w_packed.shape[0]
+    if tuple(w_packed.shape[1:]) != (ksize, ksize, Cin):
+        raise AttnShiftError(f"conv2d_nhwc: weight {tuple(w_packed.shape)} for ksize {ksize}, Cin {Cin}")
+    if act not in ("none", "relu"):
+        raise AttnShiftError(f"conv2d_nhwc: act {act!r} (none or relu)")
+    if x.dtype != torch.bfloat16:
+        raise AttnShiftError(f"expected {torch.bfloat16}, got {x.dtype}")
+    if x.stride()[1:] != (W * Cin, Cin, 1) or (B > 1 and (x.stride(0) % 8 or x.stride(0) < H * W * Cin)):
+        x = x.contiguous()
+    bs = x.stride(0) if B > 1 else H * W * Cin
+    _chk(w_packed, dtype=torch.bfloat16)
+    _chk(bias, dtype=torch.float32)
+    _chk(add, dtype=torch.bfloat16)
+    Ha = Wa = 0
+    if add is not None:
+        if add.dim() != 4 or add.shape[0] != B or add.shape[3] != Cout:
+            raise AttnShiftError(f"conv2d_nhwc: add {tuple(add.shape)} for an output [{B},{H},{W},{Cout}]")
+        Ha, Wa = int(add.shape[1]), int(add.shape[2])
+    out_dtype = torch.bfloat16 if out_dtype is None else out_dtype
+    out = torch.empty(B, H, W, Cout, device=x.device, dtype=out_dtype)
+    with _timed("conv2d"):
+        _lib.check(lib.as_conv2d_fwd(_p(x), int(bs), _p(w_packed), _p(bias), _p(add), Ha, Wa, B, H, W, Cin, Cout, int(ksize),
+                                     1 if act == "relu" else 0, AS_BF16 if out_dtype == torch.bfloat16 else AS_F32, _p(out),
+                                     _stream()), "as_conv2d_fwd")
+    return out
+
+
 def _scale_arg(delta_scale, x, delta):
     """(pointer holder, rows per scale) of a per-sample delta scale [B] for x [B, N, D] (DropPath); None -> (None, 1)."""
     if delta_scale is None:

@@ -87,6 +87,8 @@ def build_from_cfg(cfg, registry, default_args=None):
 BACKBONES = Registry("backbone")
 HEADS = Registry("head")
 ROI_HEADS = HEADS                      # mmdet 2.11: roi heads live in HEADS
+NECKS = Registry("neck")
+DETECTORS = Registry("detector")
 
 
 def build_backbone(cfg):
@@ -95,6 +97,17 @@ def build_backbone(cfg):
 
 def build_head(cfg):
     return HEADS.build(cfg)
+
+
+def build_neck(cfg):
+    return NECKS.build(cfg)
+
+
+def build_detector(cfg, train_cfg=None, test_cfg=None):
+    """mmdet/models/builder.py build_detector: train_cfg / test_cfg either inside the model dict or beside it"""
+    if (train_cfg is not None and "train_cfg" in cfg) or (test_cfg is not None and "test_cfg" in cfg):
+        raise ValueError("build_detector: train_cfg / test_cfg given both in the model dict and as arguments")
+    return DETECTORS.build(cfg, default_args=dict(train_cfg=train_cfg, test_cfg=test_cfg))
 
 
 # registered here only: these have no losses, and mmdet's own classes of the same names train with theirs

@@ -4,8 +4,9 @@
                       scale-major; single_level_grid_anchors).  Only the base anchors [L,A,4] reach the device route:
                       csrc/rpn.hip computes an anchor from (level, index); grid_anchors serves the tensor-op route and tests.
     RPNHead           mmdet/models/dense_heads/rpn_head.py:16-47, 82-236 + rpn_test_mixin.py simple_test_rpn + AnchorHead.
-                      get_bboxes: the 3x3 convolution, ReLU, the two 1x1 convolutions (through torch: plumbing), then
-                      inference.rpn_proposals.  Parameter names are the reference's (rpn_conv, rpn_cls, rpn_reg), so its
+                      get_bboxes: the 3x3 convolution, ReLU, the two 1x1 convolutions (through torch by default; with
+                      compute_dtype=torch.bfloat16, on device inputs under no-grad, two launches of as_conv2d_fwd per
+                      level), then inference.rpn_proposals.  Parameter names are the reference's (rpn_conv, rpn_cls, rpn_reg), so its
                       checkpoints load.
     RPNHead.loss /    AnchorHead.loss (mmdet/models/dense_heads/anchor_head.py:425-493) as RPNHead.loss renames it
     forward_train     (rpn_head.py:49-80) and BaseDenseHead.forward_train (base_dense_head.py:22-59): the anchor targets,
@@ -16,7 +17,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import inference, rpn_train
+from . import inference, ops, rpn_train
+from .neck import PackedConvCache, nhwc_bf16, warn_once
 from .registry import HEADS
 
 
@@ -69,8 +71,12 @@ class AnchorGenerator:
 @HEADS.register_module()
 class RPNHead(nn.Module):
     def __init__(self, in_channels, feat_channels=256, anchor_generator=None, bbox_coder=None, loss_cls=None, loss_bbox=None,
-                 train_cfg=None, test_cfg=None, **unused):
+                 train_cfg=None, test_cfg=None, compute_dtype=None, **unused):
         super().__init__()
+        if compute_dtype not in (None, torch.bfloat16):
+            raise ValueError(f"RPNHead: compute_dtype={compute_dtype!r} (None: the convolutions through torch; torch.bfloat16: "
+                             "as_conv2d_fwd on device inputs under no-grad)")
+        self.compute_dtype = compute_dtype
         ag = dict(anchor_generator or dict(scales=[8], ratios=[0.5, 1.0, 2.0], strides=[4, 8, 16, 32, 64]))
         if ag.pop("type", "AnchorGenerator") != "AnchorGenerator":
             raise ValueError("RPNHead: only AnchorGenerator anchors")
@@ -93,6 +99,7 @@ class RPNHead(nn.Module):
         self.rpn_cls = nn.Conv2d(feat_channels, self.num_anchors, 1)
         self.rpn_reg = nn.Conv2d(feat_channels, self.num_anchors * 4, 1)
         self.register_buffer("base_anchors", torch.stack(self.anchor_generator.base_anchors), persistent=False)
+        self._packed = PackedConvCache()
         self.init_weights()
 
     def init_weights(self):
@@ -101,12 +108,31 @@ class RPNHead(nn.Module):
             nn.init.constant_(m.bias, 0)
 
     def forward_single(self, x):
+        if x.dtype != self.rpn_conv.weight.dtype:                # (the neck's bf16 maps on the tensor-op route)
+            x = x.to(self.rpn_conv.weight.dtype)
         x = F.relu(self.rpn_conv(x), inplace=True)
         return self.rpn_cls(x), self.rpn_reg(x)
 
+    def _forward_single_hip(self, x):
+        """forward_single as two launches of as_conv2d_fwd (csrc/conv.hip): the 3x3 trunk with ReLU in bf16, then rpn_cls |
+        rpn_reg as ONE 1x1 convolution (A + 4A rows padded to 16) in fp32.  The two slices of its packed output leave as the
+        dense [B,A,H,W] / [B,4A,H,W] tensors inference.rpn_proposals takes (15 of 16 channels: small copies)."""
+        A = self.num_anchors
+        w, b = self._packed.get("conv", [self.rpn_conv.weight], [self.rpn_conv.bias])
+        t = ops.conv2d_nhwc(nhwc_bf16(x), w, b, ksize=3, act="relu")
+        w, b = self._packed.get("heads", [self.rpn_cls.weight, self.rpn_reg.weight], [self.rpn_cls.bias, self.rpn_reg.bias])
+        y = ops.conv2d_nhwc(t, w, b, ksize=1, out_dtype=torch.float32).permute(0, 3, 1, 2)
+        return y[:, :A].contiguous(), y[:, A:5 * A].contiguous()
+
     def forward(self, feats):
         """feats: per level [B, in_channels, H_l, W_l] -> (cls_scores, bbox_preds), two per-level lists"""
-        outs = [self.forward_single(x) for x in feats]
+        hip = self.compute_dtype == torch.bfloat16 and not torch.is_grad_enabled() and all(x.is_cuda for x in feats)
+        if hip and (self.in_channels % 32 or self.feat_channels % 32):
+            warn_once(("RPNHead", self.in_channels, self.feat_channels),
+                      f"RPNHead: channels {self.in_channels} -> {self.feat_channels} miss as_conv2d_fwd's contract (multiples "
+                      "of 32): taking the tensor-op route")
+            hip = False
+        outs = [self._forward_single_hip(x) if hip else self.forward_single(x) for x in feats]
         return [o[0] for o in outs], [o[1] for o in outs]
 
     def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None):

@@ -90,6 +90,24 @@ int as_linear_sk_fwd(const void* x, const void* W, const float* bias, void* out,
 int as_deconv2x2_fwd(const void* x, const void* W4, const float* bias4, void* out, int M, int w, int cin, int cout,
                      int dtype, int act, as_stream_t stream);
 
+/* nn.Conv2d(Cin, Cout, ksize, stride 1, padding (ksize - 1) / 2), ksize 1 or 3, on a channels-last map as an implicit GEMM
+ * over its pixels (no im2col buffer, no padded copy): the FPN's lateral and output convolutions
+ * (mmdet/models/necks/fpn.py:170-204) and the RPN trunk (mmdet/models/dense_heads/rpn_head.py forward_single).
+ *   x    bf16 [B, H, W, Cin], every image dense, image b at x + b * x_batch_stride elements (a view into a token tensor is
+ *        read in place); w bf16 [Cout, ksize, ksize, Cin] (tap-major); bias fp32 [Cout] or NULL;
+ *   add  bf16 [B, Ha, Wa, Cout] or NULL: out[b, y, x, :] += add[b, sy(y), sx(x), :] with ATen's nearest source index
+ *        sy(y) = min((int)floorf(y * ((float)Ha / H)), Ha - 1) -- F.interpolate(size=, mode='nearest') of the level above
+ *        (fpn.py:180-190); Ha <= H, Wa <= W;
+ *   out  [B, H, W, Cout] in out_dtype (AS_BF16 / AS_F32) = act(fp32 accumulator + bias + float(add)), one rounding;
+ *        act 0 = none, 1 = ReLU.  Taps outside the image contribute exact zeros.  A pure function of its inputs (no
+ *        atomics, no split-K): bitwise reproducible.
+ * Cin % 32 == 0, Cout % 16 == 0, x_batch_stride % 8 == 0, 16-byte aligned pointers (else AS_E_BADARG); the input must span
+ * less than 2^31 bytes (AS_E_UNSUPPORTED).  as_conv2d_tile_n: the output channels per tile of the variant the launcher
+ * takes for Cout (128 or 32; a host function). */
+int as_conv2d_tile_n(int Cout);
+int as_conv2d_fwd(const void* x, long long x_batch_stride, const void* w, const float* bias, const void* add, int Ha, int Wa,
+                  int B, int H, int W, int Cin, int Cout, int ksize, int act, int out_dtype, void* out, as_stream_t stream);
+
 /* QKV projection with the head split fused into the epilogue (vision_transformer.py:75-77):
  *   k : [B,h,Npad,64]   vt : [B,h,64,Npad]  (V transposed so the P.V MFMA reads keys contiguously)
  *   q : [B,h,Npad,64] elements, FRAGMENT-MAJOR inside every 32-row x 64-d tile: element (r, d) of a tile sits at

@@ -18,5 +18,6 @@ python tools/gen_golden_mmdet_pure.py
 python tools/gen_golden_point_loss.py
 python tools/gen_golden_rpn.py                # rpn (anchors, RPNHead._get_bboxes)
 python tools/gen_golden_rpn_loss.py           # rpn_loss (anchor targets, assigner, sampler, AnchorHead.loss)
+python tools/gen_golden_fpn.py                # fpn (FPN.__init__ / init_weights / forward)
 python tools/gen_golden_sampler.py
 ls -la tests/golden
